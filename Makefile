@@ -2,7 +2,7 @@
 PY ?= python
 ENV_DIR ?= .tt-env
 
-.PHONY: build test test-gpu sanitize bench bench-query bench-query-e2e images up down status metrics validate what-if docs docs-local build-docs-website pipeline clean
+.PHONY: build test test-gpu sanitize bench bench-full bench-query bench-query-e2e images up down status metrics validate what-if docs docs-local build-docs-website pipeline clean
 
 build:            ## compile native engines, sidecar data plane, load generator and gfx950 HIP kernels in-tree
 	$(PY) -c "import __graft_entry__ as g; g.build()"
@@ -18,6 +18,9 @@ sanitize:         ## native engines + backing front under ThreadSanitizer and AS
 
 bench:            ## end-to-end createTask throughput (one JSON line)
 	$(PY) bench.py
+
+bench-full:       ## the same, followed by every secondary run (browser session, envelope, KEDA, ...)
+	$(PY) bench.py --full
 
 bench-query:      ## GPU state-query scan microbenchmark (scan + ordering)
 	$(PY) bench_query.py --sorted

@@ -17,14 +17,17 @@ resource limits) and load enters where a browser's does -- the frontend's Create
 One step = ``--batch`` creates with ``--concurrency`` in flight; a step ends only when the
 processor's subscription completed every message of the batch (persisted AND delivered AND
 acknowledged).  ``config`` states the entry, mTLS, the RU/s budget, the CPU limits and every
-replica count; ``config.api_sidecar_direct`` is a second, shorter run in the same environment
-with load sent straight to the API sidecars' invoke (round 2's headline topology).
+replica count.  A plain run does the headline only; ``--full`` adds the secondary runs after
+it (``config.browser_flow``, ``browser_session``, ``external_ingest``, ``api_protocol_alt``,
+``durable``, ``reference_envelope``, and ``config.api_sidecar_direct``: a second, shorter run in
+the same environment with load sent straight to the API sidecars' invoke, round 2's headline
+topology).  ``--dump-outputs DIR`` writes the last timed step's stored tasks as ``.npy`` arrays.
 ``--entry api-sidecar`` runs round 2's hand-assembled ``LocalStack`` instead.
 
 Each rank runs its own environment (weak scaling, like adding Container Apps environments);
 rank 0 prints ONE JSON line with the aggregate tasks/s (time = max over ranks).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -48,6 +51,15 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run every secondary measurement (browser_flow, "
+                         "browser_session, external_ingest, api_sidecar_direct, api_protocol_alt, durable, "
+                         "reference_envelope with its KEDA stage, the sweeps' span attribution); without it a run "
+                         "sets up, warms up, times --steps steps and prints the result line, and the secondary "
+                         "blocks of config are null whatever their own options say")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step left in the state store (one task per "
+                         "create of the step, read back and ordered by the create's index) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=16384,
                     help="createTask requests per step per rank (the step quantum: 20 steps >= 3 s timed)")
     ap.add_argument("--concurrency", type=int, default=0,
@@ -418,6 +430,74 @@ def _collection_stats(backing: str) -> dict:
         return {"error": repr(e)}
 
 
+def _last_created(shards: list[str], n: int) -> list[dict]:
+    """The ``n`` tasks created last (ORDER BY taskCreatedOn DESC over every shard of the task
+    collection): a step ends only once its whole batch is stored and acknowledged, so after the
+    timed steps these are the last step's tasks."""
+    import urllib.request
+    q = json.dumps({"filter": {"EQ": {"isCompleted": False}}, "sort": [{"key": "taskCreatedOn", "order": "DESC"}],
+                    "page": {"limit": n}}).encode()
+    docs: list[dict] = []
+    for b in shards:
+        req = urllib.request.Request(f"{b}/cosmos/taskstracker-state-store/tasksmanagerdb/taskscollection/query", data=q,
+                                     headers={"x-tt-identity": "platform-admin", "Content-Type": "application/json"})
+        with urllib.request.urlopen(req, timeout=120) as r:
+            for res in json.loads(r.read()).get("results") or []:
+                doc = res.get("data")
+                doc = json.loads(doc) if isinstance(doc, str) else doc
+                if isinstance(doc, dict):
+                    docs.append(doc)
+    docs.sort(key=lambda t: str(t.get("taskCreatedOn", "")), reverse=True)
+    return docs[:n]
+
+
+def output_arrays(docs: list[dict], batch: int) -> dict:
+    """The last step's tasks as arrays of ``batch`` rows, row i = the step's i-th create (the
+    index in its ``taskName``), whatever order the creates were served in: how many tasks the row
+    has (1 per rank), and the stored fields that do not depend on the run's clock or its random
+    ids -- the due date in days since 1970-01-01 (-1 for a date before today: those bodies are
+    due "yesterday"), the assignee's number, ``isCompleted`` and ``isOverDue`` (the overdue
+    sweeps have marked every past-due task once drained)."""
+    from datetime import datetime
+
+    import numpy as np
+
+    from aca_dotnet_workshop_amd.models import today
+    out = {k: np.zeros(batch, np.float64) for k in ("tasks", "due_date_days", "assigned_to", "is_completed", "is_overdue")}
+    out["due_date_days"][:] = np.nan
+    out["assigned_to"][:] = np.nan
+    midnight, epoch = today(), datetime(1970, 1, 1)
+    for t in docs:
+        try:
+            i = int(str(t.get("taskName", "")).rsplit(" ", 1)[-1])
+            due = datetime.fromisoformat(str(t.get("taskDueDate", ""))[:19])
+            who = int("".join(ch for ch in str(t.get("taskAssignedTo", "")).split("@")[0] if ch.isdigit()))
+        except ValueError:
+            continue  # not one of this run's bodies
+        if not 0 <= i < batch:
+            continue
+        out["tasks"][i] += 1
+        out["due_date_days"][i] = -1.0 if due < midnight else float((due - epoch).days)
+        out["assigned_to"][i] = who
+        out["is_completed"][i] = float(bool(t.get("isCompleted")))
+        out["is_overdue"][i] = float(bool(t.get("isOverDue")))
+    return out
+
+
+def dump_outputs(out_dir: str, shards: list[str], batch: int, world: int, sweeper: "OverdueSweeper | None") -> None:
+    """``--dump-outputs``: the overdue job is fired until it marks nothing more (so ``isOverDue``
+    does not depend on when the last sweep ran), then the last step's tasks are read back from
+    the store and written as ``<name>.npy``."""
+    import numpy as np
+    if sweeper is not None:
+        sweeper.drain(0)
+    arrays = output_arrays(_last_created(shards, batch * world), batch)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    progress(f"outputs: {len(arrays)} arrays of {batch} rows in {out_dir}")
+
+
 def run_loadgen(exe: str, socks: list[str], counts_url: str | list[str], steps: int, batch: int, conc: int,
                 bodies_file: str, shared: tuple[int, int] | None = None) -> tuple[float, dict]:
     """Closed-loop load from the native generator; returns (wall seconds, its report).
@@ -633,6 +713,8 @@ def main_localstack(a: argparse.Namespace, d: Dist, cores: float, pinned) -> Non
             delivery = {"enqueued": c.get("enqueued"), "completed": c.get("completed"), "received": c.get("received"),
                         "dead_lettered": c.get("dead_letter"), "expected": sent,
                         "exactly_once": c.get("completed") == c.get("received") == c.get("enqueued") == sent}
+        if a.dump_outputs and d.rank == 0:
+            dump_outputs(a.dump_outputs, shards if shared else [doc_backing], a.batch, d.world if shared else 1, sweeper)
         total = a.batch * a.steps * (d.world if d.world > 1 else 1)
         value = total / dt_max if dt_max > 0 else 0.0
         if d.rank == 0:
@@ -1771,11 +1853,15 @@ def main_frontend(a: argparse.Namespace, d: Dist, cores: float, pinned) -> None:
             delivery = {"enqueued": c.get("enqueued"), "completed": c.get("completed"), "received": c.get("received"),
                         "dead_lettered": c.get("dead_letter"), "expected": sent,
                         "exactly_once": c.get("completed") == c.get("received") == c.get("enqueued") == sent}
+        if a.dump_outputs and d.rank == 0:
+            dump_outputs(a.dump_outputs, shards if shared else [backing], a.batch, d.world if shared else 1, sweeper)
+        # everything below the headline is a run of its own, behind --full
+        more = a.full and not shared
         # the read path at the headline's replica counts: browsers with their own
         # identity cookie (bounded task lists) post Create and follow its 302 to Tasks/Index,
         # which lists the user's tasks through the API (Index.cshtml.cs:48 -> TasksController.Get)
         browser = None
-        bsteps = 0 if shared else a.browser_steps if a.browser_steps >= 0 else max(1, a.steps // 4)
+        bsteps = 0 if not more else a.browser_steps if a.browser_steps >= 0 else max(1, a.steps // 4)
         if bsteps:
             progress(f"browser_flow: {bsteps} steps of create + follow to Tasks/Index")
             af = "; ".join(c for c in cookie.split("; ") if not c.startswith("TasksCreatedByCookie="))
@@ -1796,20 +1882,20 @@ def main_frontend(a: argparse.Namespace, d: Dist, cores: float, pinned) -> None:
         # the whole browser session at the headline's replica counts: create, list,
         # Edit GET / POST, Complete, Delete, list -- every UI handler and API route of the reference
         session = None
-        sflows = 0 if shared else a.session_flows if a.session_flows >= 0 else a.batch
+        sflows = 0 if not more else a.session_flows if a.session_flows >= 0 else a.batch
         if sflows:
             progress(f"browser_session: {sflows} flows of 7 pages")
             session = run_session(exe, targets, cookie, token, sflows, conc, root, ca_file, a.batch)
         # §3.4 external-task ingestion: storage queue -> processor -> API -> blob
         ingest = ingest_hot = None
-        if a.ingest_messages > 0 and not shared:
+        if a.ingest_messages > 0 and more:
             progress(f"external_ingest: {a.ingest_messages} queue messages")
             ingest = external_ingest(env, a.ingest_messages)
             ingest_hot = ingest.pop("hot_threads", None)
         # the same environment, load straight at the API sidecars' invoke (round 2's topology);
         # not in a shared environment (its counters are global: the two loads would mix)
         direct = None
-        dsteps = 0 if shared else a.direct_steps if a.direct_steps >= 0 else max(1, a.steps // 4)
+        dsteps = 0 if not more else a.direct_steps if a.direct_steps >= 0 else max(1, a.steps // 4)
         progress(f"timed region done: {dt:.2f} s")
         if dsteps:
             progress(f"api_sidecar_direct: {dsteps} steps")
@@ -1823,7 +1909,7 @@ def main_frontend(a: argparse.Namespace, d: Dist, cores: float, pinned) -> None:
                       "create_latency_p50_ms": drep["latency_ms"]["p50"], "create_latency_p99_ms": drep["latency_ms"]["p99"],
                       "note": "same environment, load at the API sidecars' invoke (no frontend, no mTLS hop)"}
         trace = None
-        if sweep_info is not None:  # span exporters flush at least once a second
+        if sweep_info is not None and a.full:  # span exporters flush at least once a second
             if not dsteps:
                 time.sleep(1.5)
             trace = sweep_trace(str(env.ctl.dir / "telemetry"), sweeper.sampled_trace_ids + sweeper.trace_ids, None)
@@ -1832,8 +1918,8 @@ def main_frontend(a: argparse.Namespace, d: Dist, cores: float, pinned) -> None:
             sweep_info["trace_top_spans_p50_ms"] = dict(sorted(spans.items(), key=lambda kv: -kv[1])[:4])
             sweep_info["trace_of"] = "the warmup's sampled sweeps (the timed region's are unsampled)"
         envelope = alt = None
-        asteps = 0 if shared else a.alt_steps if a.alt_steps >= 0 else max(2, a.steps // 2)
-        if (a.envelope_s > 0 or asteps) and not shared:  # after the headline's environment is down
+        asteps = 0 if not more else a.alt_steps if a.alt_steps >= 0 else max(2, a.steps // 2)
+        if (a.envelope_s > 0 or asteps) and more:  # after the headline's environment is down
             env.stop()
         durable = None
         if asteps:
@@ -1843,7 +1929,7 @@ def main_frontend(a: argparse.Namespace, d: Dist, cores: float, pinned) -> None:
             progress(f"durable: {asteps} steps with the backing's logs on group commit")
             durable = protocol_alt(a, overrides, exe, root, asteps, conc, d.rank, durable=True)
             progress("durable done")
-        if a.envelope_s > 0 and not shared:
+        if a.envelope_s > 0 and more:
             if d.rank == 0:
                 progress(f"reference envelope: {a.envelope_s:g} s")
                 envelope = reference_envelope(exe, root, a.envelope_s, d.rank)

@@ -33,7 +33,7 @@ def _check(line: dict, n: int, steps: int, warmup: int) -> None:
 
 def test_bench_single_process():
     env = dict(os.environ, PYTHONPATH=str(ROOT))
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "32",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "32",
                         "--api-replicas", "1", "--processor-replicas", "1", "--envelope-s", "4",
                         "--keda-messages", "300", "--ingest-messages", "64"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -128,16 +128,44 @@ def test_thread_cpu_and_hot_threads():
                              2.0) == [["a", "x", 0.5, 0.5], ["b", "y", 0.25, 1.0]]
 
 
-def test_bench_api_sidecar_entry_single_process():
-    """--entry api-sidecar (round 2's topology, kept as a secondary mode) on one rank."""
+def test_bench_api_sidecar_entry_single_process(tmp_path):
+    """--entry api-sidecar (round 2's topology, kept as a secondary mode) on one rank; a plain
+    run (no --full), with --dump-outputs: the last step's 32 tasks read back from the store."""
+    import numpy as np
     env = dict(os.environ, PYTHONPATH=str(ROOT))
     r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "32", "--entry",
-                        "api-sidecar", "--api-replicas", "1", "--processor-replicas", "1"],
+                        "api-sidecar", "--api-replicas", "1", "--processor-replicas", "1",
+                        "--past-due-every", "8", "--dump-outputs", str(tmp_path / "out")],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1 and lines[0]["config"]["entry"] == "api-sidecar"
     _check(lines[0], 1, 2, 1)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(got) == {"tasks", "due_date_days", "assigned_to", "is_completed", "is_overdue"}
+    assert all(v.shape == (32,) and v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["tasks"], np.ones(32))  # each create of the last step stored once
+    assert np.array_equal(got["assigned_to"], np.arange(32) % 13) and not got["is_completed"].any()
+    past = np.arange(32) % 8 == 0  # due yesterday: marked overdue by the sweeps, the others are not
+    assert np.array_equal(got["due_date_days"] == -1.0, past) and np.array_equal(got["is_overdue"] == 1.0, past)
+    assert (got["due_date_days"][~past] == 21915.0).all()  # 2030-01-01
+
+
+def test_output_arrays_rows_follow_the_create_index():
+    """bench.output_arrays: rows by the index in taskName whatever order the tasks come in;
+    tasks that are not this run's bodies, or beyond the batch, are left out."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    from bench import output_arrays
+
+    def task(i, due="2030-01-01T00:00:00", over=False):
+        return {"taskName": f"bench task {i}", "taskDueDate": due, "taskAssignedTo": f"assignee{i % 13}@bench.local",
+                "isCompleted": False, "isOverDue": over}
+    docs = [task(2), task(0, "2001-02-03T00:00:00", True), task(2), task(7), {"taskName": "other"}]
+    got = output_arrays(docs, 4)
+    assert got["tasks"].tolist() == [1.0, 0.0, 2.0, 0.0]
+    assert got["due_date_days"][0] == -1.0 and got["due_date_days"][2] == 21915.0 and np.isnan(got["due_date_days"][1])
+    assert got["is_overdue"].tolist() == [1.0, 0.0, 0.0, 0.0] and got["assigned_to"][2] == 2.0
 
 
 def test_bench_two_ranks_torchrun():

@@ -40,7 +40,8 @@ def test_gc_log_reports_full_collections_with_survivor_types(tmp_path):
 
 def test_native_loop_busy_notes(tmp_path, monkeypatch):
     """A native event loop attached to its GapTracer reports iterations busier than TT_STALL_MS
-    (here 1 µs: every iteration that handled a request) as loop-busy lines."""
+    (here 10 µs, the resolution the lines print ``ms`` at -- a shorter iteration would read 0.00:
+    the iterations that handled a request) as loop-busy lines."""
     import asyncio
     import sys
     from pathlib import Path
@@ -49,7 +50,7 @@ def test_native_loop_busy_notes(tmp_path, monkeypatch):
     from helpers import run
     log = tmp_path / "stall.jsonl"
     monkeypatch.setenv("TT_STALL_LOG", str(log))
-    monkeypatch.setenv("TT_STALL_MS", "0.001")
+    monkeypatch.setenv("TT_STALL_MS", "0.01")
 
     async def main():
         async with Env("native", tmp_path) as e:

@@ -60,10 +60,10 @@ def test_job_graph_skips_dependants_of_skipped_jobs():
 
 # -- the pipelines, run --------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def published(tmp_path_factory):
+def published(module_tmp_path):
     """publish-images.yml: the paths filter picks the changed services, a matrix job builds each
     with the platform's OCI builder and pushes latest / branch / sha to the `ghcr` registry."""
-    base = tmp_path_factory.mktemp("cicd")
+    base = module_tmp_path
     os.environ["TT_CONTAINER_REGISTRY_ROOT"] = str(base / "registries")
     res = P.run(P.load(GH / "publish-images.yml"),
                 {"github": {"changed_files": SERVICES + ["README.md"], "ref_name": "feature/x", "sha": "abc1234"}})
