@@ -76,6 +76,10 @@ def load_library(build: bool = True) -> ctypes.CDLL:
     lib.tt_stream_sync.restype = ctypes.c_int
     lib.tt_tile_rows.restype = ctypes.c_int
     lib.tt_max_depth.restype = ctypes.c_int
+    lib.tt_max_lds_bitmap_words.restype = ctypes.c_int
+    lib.tt_max_lds_ranks.restype = ctypes.c_int
+    lib.tt_max_lds_groups.restype = ctypes.c_int
+    lib.tt_lds_rank_words.restype = ctypes.c_int
     _lib = lib
     return lib
 

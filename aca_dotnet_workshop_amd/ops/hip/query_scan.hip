@@ -213,6 +213,9 @@ tt_scan_compact_w(const uint32_t* __restrict__ mask32, const int32_t* __restrict
 // thread with one 16/32/64-byte load and store per thread (a full re-encode of 1e8 rows is a
 // streaming pass), the unaligned head and tail row by row.
 namespace {
+constexpr int kMaxLdsRanks = 8192;   // tt_rank_encode: rank table entries staged in LDS (32 KiB)
+constexpr int kMaxLdsGroups = 8192;  // tt_group_count: LDS-privatised counters (32 KiB)
+
 __device__ __forceinline__ int32_t rank_of(int32_t id, const int32_t* lds_rank, const int32_t* rank_table,
                                            int32_t nranks, bool staged) {
   return (id >= 0 && id < nranks) ? (staged ? lds_rank[id] : rank_table[id]) : -1;
@@ -229,7 +232,7 @@ extern "C" __global__ void __launch_bounds__(kBlock)
 tt_rank_encode(const ColumnDesc* __restrict__ src, const int32_t* __restrict__ rank_table, int32_t nranks,
                int64_t lo, int64_t hi, uint64_t dst_ptr, int32_t dst_width) {
   extern __shared__ int32_t lds_rank[];
-  const bool staged = nranks <= 8192;
+  const bool staged = nranks <= kMaxLdsRanks;
   if (staged)
     for (int i = threadIdx.x; i < nranks; i += kBlock) lds_rank[i] = rank_table[i];
   __syncthreads();
@@ -286,7 +289,7 @@ extern "C" __global__ void __launch_bounds__(kBlock)
 tt_group_count(const ColumnDesc* __restrict__ cols, int32_t g, const uint16_t* __restrict__ mask, int64_t nrows,
                int32_t ngroups, uint32_t* __restrict__ counts) {
   extern __shared__ uint32_t hist[];
-  const bool use_lds = ngroups <= 8192;
+  const bool use_lds = ngroups <= kMaxLdsGroups;
   if (use_lds)
     for (int i = threadIdx.x; i < ngroups; i += kBlock) hist[i] = 0;
   __syncthreads();
@@ -367,7 +370,7 @@ extern "C" int tt_launch_group_count(const void* cols, int32_t g, const uint16_t
   int64_t blocks = (nslices + kBlock - 1) / kBlock;
   if (blocks > 2048) blocks = 2048;
   if (blocks == 0) return 0;
-  const size_t lds = ngroups <= 8192 ? (size_t)ngroups * sizeof(uint32_t) : 0;
+  const size_t lds = ngroups <= kMaxLdsGroups ? (size_t)ngroups * sizeof(uint32_t) : 0;
   hipLaunchKernelGGL(tt_group_count, dim3((unsigned)blocks), dim3(kBlock), lds, stream,
                      reinterpret_cast<const ColumnDesc*>(cols), g, mask, nrows, ngroups, counts);
   return (int)hipGetLastError();
@@ -380,7 +383,7 @@ extern "C" int tt_launch_rank_encode(const void* src, const int32_t* rank_table,
   int64_t blocks = ((hi - lo + 15) / 16 + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  const size_t lds = nranks <= 8192 ? (size_t)nranks * sizeof(int32_t) : 0;
+  const size_t lds = nranks <= kMaxLdsRanks ? (size_t)nranks * sizeof(int32_t) : 0;
   hipLaunchKernelGGL(tt_rank_encode, dim3((unsigned)blocks), dim3(kBlock), lds, stream,
                      reinterpret_cast<const ColumnDesc*>(src), rank_table, nranks, lo, hi, (uint64_t)dst, dst_width);
   return (int)hipGetLastError();
@@ -388,3 +391,6 @@ extern "C" int tt_launch_rank_encode(const void* src, const int32_t* rank_table,
 
 extern "C" int tt_tile_rows() { return kTileRows; }
 extern "C" int tt_max_depth() { return kMaxDepth; }
+extern "C" int tt_max_lds_bitmap_words() { return kMaxLdsBitmapWords; }
+extern "C" int tt_max_lds_ranks() { return kMaxLdsRanks; }
+extern "C" int tt_max_lds_groups() { return kMaxLdsGroups; }

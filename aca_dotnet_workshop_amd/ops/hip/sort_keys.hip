@@ -128,6 +128,7 @@ extern "C" int tt_launch_sort_keys(const void* cols, const int32_t* rows, int64_
 }
 
 extern "C" int tt_sort_max_keys() { return kMaxKeys; }
+extern "C" int tt_lds_rank_words() { return kLdsRankWords; }
 
 // ---------------------------------------------------------------------------------------
 // Top-k by radix select: a paged, ordered query needs only the first `k` keys of the
