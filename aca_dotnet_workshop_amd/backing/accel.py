@@ -4,7 +4,9 @@ Planner: a filter the native engine can answer from its hash indexes (every AND 
 an EQ/IN leaf; every OR branch is indexable) stays native -- O(matches).  Anything that
 needs a collection scan (ranges, NEQ, OR over non-equality leaves, no filter with a sort)
 runs on the collection's ``ColumnarIndex``: on the GPU (``ops/hip/query_scan.hip``) when a
-HIP device is present, else the NumPy executor of the same compiled program.
+HIP device is present, else the NumPy executor of the same compiled program.  Grouped
+aggregates (``aggregate``: COUNT/SUM/AVG/MIN/MAX per group) always scan, so they go to the index
+whenever the collection has one or is large enough (``ops/hip/group_agg.hip`` on the GPU).
 
 The index is fed by the document store's own column mirror (``DocStore.mirror_*``,
 native/src/docstore.hpp): every write -- from the GIL-free native HTTP front or from
@@ -35,7 +37,7 @@ import threading
 import time
 from typing import Any
 
-from ..ops.columnar import ColumnarIndex, Unsupported, filter_paths
+from ..ops.columnar import ColumnarIndex, Unsupported, filter_paths, parse_aggregate
 
 log = logging.getLogger("backing.accel")
 PREFIX_PATH = "\x00keyprefix"
@@ -240,6 +242,46 @@ class CollectionAccelerator:
                         select_ms=t_sel * 1e3, results_ms=t_res * 1e3)
             for key, v in self.index.timing.items():  # the paged device path's own breakdown
                 self.stats[key] = round(v, 3)
+            return out
+
+    def aggregate(self, q: dict[str, Any], prefix: str, store, hist: bool = False) -> dict[str, Any] | None:
+        """Grouped aggregates (``ColumnarIndex.aggregate``) from the mirror at its sync point, or
+        None to let the caller aggregate the native engine's documents.  Always a scan, so the
+        hash-index shortcut of ``query`` does not apply; no row goes back to the store.
+        Blocking.  ValueError: a malformed request."""
+        spec = parse_aggregate(q)
+        if self.disabled or not (self.index is not None or len(store) >= self.min_docs):
+            self.stats["native"] += 1
+            return None
+        t_wait = time.perf_counter()
+        with self.lock:
+            t0 = time.perf_counter()
+            try:
+                if self.index is None:
+                    self.build(store, filter_paths(spec.filter) + spec.group_by + spec.keys)
+                else:
+                    self.index.sync()
+                t1 = time.perf_counter()
+                flt = spec.filter or {}
+                if prefix:
+                    flt = {"AND": [{"EQ": {PREFIX_PATH: prefix}}, flt]} if flt else {"EQ": {PREFIX_PATH: prefix}}
+                k = self.kernels()
+                try:
+                    out = self.index.aggregate({**q, "filter": flt}, k, hist)
+                except Unsupported:  # this request only: the mirror stays
+                    self.stats["fallback"] += 1
+                    return None
+            except Unsupported as e:
+                log.info("columnar accelerator off for this collection: %s", e)
+                self.disabled, self.index = True, None
+                self.stats["fallback"] += 1
+                return None
+            self.stats["gpu" if k is not None else "cpu"] += 1
+            t2 = time.perf_counter()
+            for key, v in (("lock_wait_ms", t0 - t_wait), ("sync_ms", t1 - t0), ("aggregate_ms", t2 - t1)):
+                self.stats[key] = round(self.stats.get(key, 0.0) + v * 1e3, 3)
+            _stall_note("accel-aggregate", t2 - t_wait, lock_wait_ms=(t0 - t_wait) * 1e3, sync_ms=(t1 - t0) * 1e3,
+                        aggregate_ms=(t2 - t1) * 1e3)
             return out
 
 

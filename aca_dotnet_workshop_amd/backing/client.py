@@ -123,6 +123,15 @@ class BackingClient:
         r = await self._req("POST", path, query, {"Content-Type": "application/json"}, what="state query")
         return r.body
 
+    async def doc_aggregate(self, account: str, db: str, coll: str, query: bytes, prefix: str = "",
+                            hist: bool = False) -> bytes:
+        """Grouped aggregates (``{"filter", "groupBy", "aggregate"}`` -> ``{"groups": [...]}``);
+        ``hist``: the raw histograms per aggregate key instead of the reduced values."""
+        args = {**({"prefix": prefix} if prefix else {}), **({"project": "hist"} if hist else {})}
+        path = f"{self._coll(account, db, coll)}/aggregate" + ("?" + urlencode(args) if args else "")
+        r = await self._req("POST", path, query, {"Content-Type": "application/json"}, what="state aggregate")
+        return r.body
+
     async def doc_transaction(self, account: str, db: str, coll: str, ops: list[dict[str, Any]]) -> None:
         await self._req("POST", f"{self._coll(account, db, coll)}/transaction", json.dumps({"ops": ops}).encode(),
                         {"Content-Type": "application/json"}, what="state transaction")

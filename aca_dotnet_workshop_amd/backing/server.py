@@ -40,6 +40,7 @@ from ..telemetry.profiler import maybe_profile
 from ..utils import gctrace
 from ..web.app import WebApp
 from ..web.http import HTTPError, Request, Response, empty, json_response, problem
+from ..ops.columnar import AggGroups, parse_aggregate
 from .accel import CollectionAccelerator, accelerator_from_env, mirror_paths_from_env
 from .auth import AccessPolicy
 
@@ -199,6 +200,30 @@ class BackingServices:
         span.set("bytes", len(body))
         span.end()
         return 200, body, [("x-tt-handler-end-mono", f"{time.monotonic():.6f}")]
+
+    def run_aggregate(self, account: str, db: str, coll: str, raw: bytes, prefix: str, hist: bool) -> tuple[int, bytes]:
+        """Grouped aggregates of the collection, after admission (``ops.columnar.parse_aggregate``
+        has the request): from the columnar / GPU accelerator, or -- accelerator off, a small or
+        a TTL collection, a filter the mirror does not take -- over the documents the native
+        engine's query returns, reduced by the same ``AggGroups`` / ``reduce_hist``.  ``hist``:
+        the raw histograms (a shard's share of a partitioned collection).  Returns (200, result
+        JSON) -- the result-size RU are debited here -- or (400, the error).  Blocking."""
+        s = self.store(account, db, coll)
+        try:
+            q = json.loads(raw.decode("utf-8") if raw else "{}")
+            spec = parse_aggregate(q)
+            res = self.accel(account, db, coll).aggregate(q, prefix, s, hist)
+            if res is None:
+                docs = json.loads(s.query(json.dumps({"filter": spec.filter} if spec.filter else {}), prefix, False))
+                groups = AggGroups(spec)
+                for r in docs["results"]:
+                    groups.add_doc(r["data"])
+                res = groups.response(hist)
+        except ValueError as ex:
+            return 400, str(ex).encode()
+        body = json.dumps(res, separators=(",", ":")).encode()
+        s.debit(s.query_ru(len(body)) - s.query_ru(0))  # result size part: owed after the fact
+        return 200, body
 
     def accel(self, account: str, db: str, coll: str) -> CollectionAccelerator:
         key = (account, db, coll)
@@ -372,6 +397,21 @@ class BackingServices:
                 return problem(status, detail=body.decode("utf-8", "replace"))
             return Response(body, 200, headers or None, "application/json")
 
+        async def aggregate(req: Request) -> Response:
+            s = st(req, "cosmos.read")
+            # ?project=hist: per group the raw (value, rows) histogram of each aggregate key --
+            # a shard's share, which the partitioned client adds up before reducing once
+            hist = (req.query_get("project", "") or "").lower() == "hist"
+            if (t := throttled(req, s, s.query_ru(0), 2)) is not None:
+                return t
+            p = req.path_params
+            status, body = await asyncio.get_running_loop().run_in_executor(
+                self.query_pool, self.run_aggregate, p["account"], p["db"], p["coll"], req.body,
+                req.query_get("prefix", "") or "", hist)
+            if status != 200:
+                return problem(status, detail=body.decode("utf-8", "replace"))
+            return Response(body, 200, None, "application/json")
+
         async def transaction(req: Request) -> Response:
             s = st(req, "cosmos.write")
             if (t := throttled(req, s, s.write_ru(len(req.body)))) is not None:
@@ -416,6 +456,7 @@ class BackingServices:
         app.add_route(base + "/bulkget", bulk_get, ("POST",))
         app.add_route(base + "/bulkset", bulk_set, ("POST",))
         app.add_route(base + "/query", query, ("POST",))
+        app.add_route(base + "/aggregate", aggregate, ("POST",))
         app.add_route(base + "/transaction", transaction, ("POST",))
         async def set_throughput(req: Request) -> Response:
             """Provision the container's RU/s (Bicep ``autoscaleSettings.maxThroughput`` /

@@ -18,6 +18,7 @@ from __future__ import annotations
 import functools
 import itertools
 import json
+import math
 import operator
 import os
 import time
@@ -135,6 +136,171 @@ def filter_paths(f: Any) -> list[str]:
         elif isinstance(arg, dict) and len(arg) == 1:
             out.append(next(iter(arg)))
     return out
+
+
+# -- grouped aggregates: the semantics, shared by every execution path -----------------------
+# GPU (hip/group_agg.hip), CPU columnar, the native engine's documents (backing/server.py) and
+# the shard merge (backing/shards.py) all reduce to per-group histograms of (value, row count)
+# held in ``AggGroups`` and finish in ``reduce_hist``: one definition, one answer.
+AGG_OPS = ("COUNT", "SUM", "AVG", "MIN", "MAX")
+MAX_GROUP_BY = 2
+
+
+def _canon(v: Any) -> Any:
+    """One representative per ``vkey`` class of numbers (1 and 1.0 are one dictionary value,
+    and which was written first differs between the paths): integral below 2^53 as int, else float."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        return v
+    f = float(v) + 0.0
+    return int(f) if f.is_integer() and abs(f) < 2.0 ** 53 else f
+
+
+def reduce_hist(hist: Iterable[tuple[Any, int]], ops: Iterable[str]) -> dict[str, Any]:
+    """The aggregates ``ops`` of one path within one group from its histogram -- (JSON value,
+    rows holding it) pairs, rows where the path is missing not among them -- undivided:
+    COUNT = rows where the path is defined; SUM over int and float values (not bool), correctly
+    rounded (``fsum``: the order of the pairs does not matter); AVG = (numeric sum, numeric
+    rows), divided last by the caller; MIN / MAX by ``compare``.  An aggregate without an
+    eligible value is left out (COUNT is 0 then)."""
+    hist = [(v, int(c)) for v, c in hist if c]
+    nums = [(v, c) for v, c in hist if type_rank(v) == 2]
+    out: dict[str, Any] = {}
+    for op in ops:
+        if op == "COUNT":
+            out[op] = sum(c for _, c in hist)
+        elif op in ("SUM", "AVG") and nums:
+            s = math.fsum(float(v) * c for v, c in nums)
+            out[op] = s if op == "SUM" else (s, sum(c for _, c in nums))
+        elif op in ("MIN", "MAX") and hist:
+            best = hist[0][0]
+            for v, _ in hist[1:]:
+                c = compare(v, best)
+                if (c < 0) if op == "MIN" else (c > 0):
+                    best = v
+            out[op] = best
+    return out
+
+
+@dataclass
+class AggSpec:
+    filter: Any
+    group_by: list[str]
+    aggs: list[tuple[str, str | None]]   # (op, key); key None = COUNT of the group's rows
+    keys: list[str]                      # the distinct aggregate keys, in request order
+
+
+def parse_aggregate(q: Any) -> AggSpec:
+    """The aggregate request body, validated (ValueError = the route's 400)."""
+    if not isinstance(q, dict):
+        raise ValueError("aggregate request must be a JSON object")
+    group_by = q.get("groupBy") or []
+    if not isinstance(group_by, list) or len(group_by) > MAX_GROUP_BY:
+        raise ValueError(f"groupBy takes at most {MAX_GROUP_BY} paths")
+    aggs: list[tuple[str, str | None]] = []
+    raw = q.get("aggregate") or []
+    if not isinstance(raw, list):
+        raise ValueError("aggregate must be an array")
+    for a in raw:
+        op = a.get("op") if isinstance(a, dict) else None
+        op = op.upper() if isinstance(op, str) else op
+        if op not in AGG_OPS:
+            raise ValueError(f"unknown aggregate op {op!r}")
+        key = a.get("key")
+        if key is None and op != "COUNT":
+            raise ValueError(f"{op} needs a key")
+        aggs.append((op, key))
+    for p in [*group_by, *(k for _, k in aggs if k is not None)]:
+        if not isinstance(p, str) or not p or p.startswith("\x00"):
+            raise ValueError("a path must be a non-empty string that does not begin with NUL")
+    flt = q.get("filter")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter must be an object")
+    return AggSpec(flt or None, list(group_by), aggs, list(dict.fromkeys(k for _, k in aggs if k is not None)))
+
+
+class AggGroups:
+    """Per group (the group-by values, a missing path apart from JSON null): its row count and,
+    per aggregate key, the histogram of the key's values.  Counts of equal groups and values
+    (``vkey``) add, so partial answers -- launches, shards -- merge by adding themselves."""
+
+    def __init__(self, spec: AggSpec) -> None:
+        self.spec = spec
+        self.groups: dict[tuple, dict[str, Any]] = {}
+        if not spec.group_by:
+            self._group(())  # no GROUP BY: one group, also over an empty selection
+
+    def _group(self, gvals: tuple) -> dict[str, Any]:
+        gk = tuple(None if v is _MISSING else vkey(v) for v in gvals)
+        g = self.groups.get(gk)
+        if g is None:
+            g = self.groups[gk] = {"values": tuple(v if v is _MISSING else _canon(v) for v in gvals), "count": 0,
+                                   "hist": {k: {} for k in self.spec.keys}}
+        return g
+
+    def add_rows(self, gvals: tuple, n: int) -> None:
+        self._group(gvals)["count"] += int(n)
+
+    def add_value(self, gvals: tuple, key: str, value: Any, n: int) -> None:
+        h = self._group(gvals)["hist"][key]
+        e = h.get(vkey(value))
+        if e is None:
+            h[vkey(value)] = [_canon(value), int(n)]
+        else:
+            e[1] += int(n)
+
+    def add_doc(self, doc: Any) -> None:
+        """One document (the path without a column mirror)."""
+        gvals = tuple(get_path(doc, p) for p in self.spec.group_by)
+        self.add_rows(gvals, 1)
+        for k in self.spec.keys:
+            v = get_path(doc, k)
+            if v is not _MISSING:
+                self.add_value(gvals, k, v, 1)
+
+    def add_response(self, res: dict[str, Any]) -> None:
+        """A ``project=hist`` answer of another store (a shard)."""
+        for g in res["groups"]:
+            gvals = tuple(g["group"].get(p, _MISSING) for p in self.spec.group_by)
+            self.add_rows(gvals, g["count"])
+            for k, pairs in g["hist"].items():
+                for v, c in pairs:
+                    self.add_value(gvals, k, v, c)
+
+    def response(self, hist: bool = False) -> dict[str, Any]:
+        """The route's answer: groups sorted by their values (``compare``, a missing path
+        first); ``hist``: the raw histograms per aggregate key instead of the reduced values."""
+        def cmp(a: dict, b: dict) -> int:
+            for x, y in zip(a["values"], b["values"]):
+                if x is _MISSING or y is _MISSING:
+                    c = (y is _MISSING) - (x is _MISSING)
+                else:
+                    c = compare(x, y)
+                if c:
+                    return c
+            return 0
+        out = []
+        for g in sorted(self.groups.values(), key=functools.cmp_to_key(cmp)):
+            if not g["count"] and self.spec.group_by:
+                continue
+            o: dict[str, Any] = {"group": {p: v for p, v in zip(self.spec.group_by, g["values"]) if v is not _MISSING},
+                                 "count": g["count"]}
+            if hist:
+                o["hist"] = {k: sorted(([v, c] for v, c in h.values()),
+                                       key=functools.cmp_to_key(lambda a, b: compare(a[0], b[0])))
+                             for k, h in g["hist"].items()}
+            else:
+                red = {k: reduce_hist(h.values(), [op for op, kk in self.spec.aggs if kk == k])
+                       for k, h in g["hist"].items()}
+                aggs = []
+                for op, k in self.spec.aggs:
+                    if k is None:
+                        aggs.append({"op": op, "value": g["count"]})
+                    elif op in red[k]:
+                        v = red[k][op]
+                        aggs.append({"op": op, "key": k, "value": v[0] / v[1] if op == "AVG" else v})
+                o["aggregates"] = aggs
+            out.append(o)
+        return {"groups": out}
 
 
 def rank_interval(c: "Column", sat: np.ndarray) -> tuple[int, int] | None:
@@ -1140,6 +1306,83 @@ class ColumnarIndex:
         ids = ids[ids >= 0]
         cnt = np.bincount(ids, minlength=len(col.values))
         return {json.dumps(col.values[i]): int(x) for i, x in enumerate(cnt) if x}
+
+    # Histogram cells the host path counts with ``np.bincount``; sparser key spaces go through
+    # ``np.unique`` (no array of all cells).  The device's own cap is ``tt_group_max_cells()``.
+    HOST_MAX_CELLS = 1 << 22
+
+    def aggregate(self, q: dict[str, Any], kernels=None, hist: bool = False) -> dict[str, Any]:
+        """Grouped aggregates over the filtered collection (``parse_aggregate`` has the request,
+        ``AggGroups.response`` the answer).  One histogram of dictionary ids over the key columns
+        (group-by..., aggregate key) per distinct aggregate key and one over (group-by...) for
+        the row counts, slot ``len(values)`` of an axis = path missing: with ``kernels`` each is
+        one fused filter + histogram launch (``hip/group_agg.hip``), without them a
+        ``np.bincount`` over the rows the CPU scan selected -- also for a histogram with more
+        cells than the device takes.  The non-zero cells decode through the dictionaries into
+        ``AggGroups``; ``reduce_hist`` finishes, the same on every path."""
+        spec = parse_aggregate(q)
+        # every referenced column first: one re-encode (source-backed) and one device upload
+        self.ensure_columns(filter_paths(spec.filter) + spec.group_by + spec.keys)
+        prog = self.compile_cached(spec.filter or {})
+        gcols = [self.col_of[p] for p in spec.group_by]
+        dev = None
+        if kernels is not None:
+            st, code, bitmaps = self.device_program(prog, kernels)
+            dev = (st, code, bitmaps, int(kernels.lib.tt_group_max_cells()))
+        host_rows: list[np.ndarray] = []  # the CPU selection, made once when a histogram needs it
+
+        def histogram(cols: list[int]) -> tuple[np.ndarray, np.ndarray, list[int]]:
+            """(non-zero cells, their counts, the axes' sizes) of the key columns ``cols``."""
+            dims = [len(self.columns[c].values) for c in cols]  # after the upload: widths match
+            ncells = math.prod(d + 1 for d in dims)
+            if ncells >= 1 << 62:
+                raise Unsupported("aggregate key space too large")
+            if dev is not None and ncells <= dev[3]:
+                counts = kernels.scan_group(dev[0]["table"], dev[0]["live"], self.cap, self.n, dev[1], dev[2],
+                                            cols, dims).cpu().numpy().view(np.uint32)
+                cells = np.nonzero(counts)[0]
+                return cells, counts[cells], dims
+            if not host_rows:
+                try:
+                    host_rows.append(self.select_native(prog))
+                except ImportError:
+                    host_rows.append(self.select_numpy(prog))
+            cell = np.zeros(host_rows[0].size, dtype=np.int64)
+            for c, d in zip(cols, dims):
+                ids = self.ids[c, host_rows[0]]
+                cell = cell * (d + 1) + np.where(ids < 0, d, ids)
+            if ncells <= self.HOST_MAX_CELLS:
+                counts = np.bincount(cell, minlength=ncells)
+                cells = np.nonzero(counts)[0]
+                return cells, counts[cells], dims
+            cells, counts = np.unique(cell, return_counts=True)
+            return cells, counts, dims
+
+        def decode(cells: np.ndarray, dims: list[int]) -> list[list[int]]:
+            slots = []
+            for d in reversed(dims):
+                cells, s = np.divmod(cells, d + 1)
+                slots.append(s.tolist())
+            return slots[::-1]
+
+        def value(col: int, slot: int) -> Any:
+            vals = self.columns[col].values
+            return vals[slot] if slot < len(vals) else _MISSING
+
+        groups = AggGroups(spec)
+        cells, counts, dims = histogram(gcols)
+        slots = decode(cells, dims)
+        for i, n in enumerate(counts.tolist()):
+            groups.add_rows(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), n)
+        for key in spec.keys:
+            kc = self.col_of[key]
+            cells, counts, dims = histogram(gcols + [kc])
+            slots = decode(cells, dims)
+            for i, n in enumerate(counts.tolist()):
+                v = value(kc, slots[-1][i])
+                if v is not _MISSING:
+                    groups.add_value(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), key, v, n)
+        return groups.response(hist)
 
     # -- full query --------------------------------------------------------------
     def order(self, rows: np.ndarray, sort: list[dict[str, Any]] | None, k: int | None = None) -> np.ndarray:

@@ -46,6 +46,9 @@ def load_library(build: bool = True) -> ctypes.CDLL:
     lib.tt_launch_scan_compact.restype = ctypes.c_int
     lib.tt_launch_group_count.argtypes = [P, I32, P, I64, I32, P, P]
     lib.tt_launch_group_count.restype = ctypes.c_int
+    lib.tt_launch_scan_group.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, P, I32, P]
+    lib.tt_launch_scan_group.restype = ctypes.c_int
+    lib.tt_group_max_cells.restype = ctypes.c_int
     lib.tt_launch_sort_keys.argtypes = [P, P, I64, P, I32, P, I32, P, I32, P, P, I32, P]
     lib.tt_launch_sort_keys.restype = ctypes.c_int
     lib.tt_sort_max_keys.restype = ctypes.c_int
@@ -346,6 +349,48 @@ class GpuKernels:
         if rc != 0:
             raise RuntimeError(f"tt_group_count launch failed ({rc})")
         return counts[:ngroups]
+
+    def scan_group(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, max_blocks: int = 0,
+                   counts=None):
+        """Histogram (device int32 holding uint32 counts, ``prod(dims[i] + 1)`` cells) of the key
+        columns' dictionary ids over the live rows satisfying ``prog``: filter and histogram in
+        one pass (``hip/group_agg.hip`` tt_scan_group).  ``keys``: up to 3 rows of ``table``;
+        ``dims``: their dictionary sizes, slot ``dims[i]`` of axis i counting the rows where the
+        path is missing; ids at or past ``dims[i]`` are dropped.  ``table`` / ``live16`` /
+        ``capacity`` as for ``select``.  ``counts``: a zeroed tensor to add into instead of a
+        new one.  ValueError when the cells exceed ``tt_group_max_cells()``."""
+        torch = self.torch
+        keys, dims = [int(x) for x in keys], [int(x) for x in dims]
+        if len(keys) != len(dims) or len(keys) > 3:
+            raise ValueError("at most 3 key columns, one dictionary size each")
+        if capacity % self.tile_rows or nrows > capacity:
+            raise ValueError("column capacity must be a multiple of the tile and >= nrows")
+        if live16.dtype != torch.int16 or live16.numel() * 16 < capacity:
+            raise ValueError("liveness mask must be int16 bits covering the capacity")
+        if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError("column table must be int64 [ncols, 2]")
+        if prog.dtype != torch.int32 or prog.ndim != 2 or prog.shape[1] != 4:
+            raise ValueError("program must be int32 [L, 4]")
+        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
+            raise ValueError("key columns must be rows of the column table, dictionary sizes >= 0")
+        ncells = 1
+        for d in dims:
+            ncells *= d + 1
+        limit = int(self.lib.tt_group_max_cells())
+        if counts is None:
+            counts = torch.zeros(min(ncells, limit), dtype=torch.int32, device=self.device)
+        elif counts.dtype != torch.int32 or counts.numel() < min(ncells, limit):
+            raise ValueError("counters must be int32, one per cell")
+        n = len(keys)
+        rc = self.lib.tt_launch_scan_group(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(), prog.shape[0],
+                                           bitmaps.data_ptr(), bitmaps.numel(), (ctypes.c_int32 * 3)(*keys),
+                                           (ctypes.c_int32 * 3)(*dims), n, counts.data_ptr(), max_blocks,
+                                           self._stream())
+        if rc == -2:
+            raise ValueError(f"{ncells} histogram cells exceed the device limit of {limit}")
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_group launch failed ({rc})")
+        return counts
 
     def sort_keys(self, table, rows, specs, ranks, seq, seq_bits: int, hist=None, shift: int = 0):
         """Packed 63-bit ordering keys (int64) for ``rows`` (int32, device): see

@@ -282,9 +282,12 @@ tt_rank_encode(const ColumnDesc* __restrict__ src, const int32_t* __restrict__ r
   }
 }
 
-// Grouped count: histogram of column `g` dictionary ids over the selected rows (the
-// "open tasks per assignee" dashboard aggregate).  LDS-privatised counters for dictionaries
-// up to 8192 entries, global atomics otherwise.
+// Grouped count: histogram of column `g` dictionary ids over the selected rows, read back from
+// the selection mask tt_scan_eval wrote.  LDS-privatised counters for dictionaries up to 8192
+// entries, global atomics otherwise.  The two-pass predecessor of tt_scan_group (group_agg.hip:
+// filter and histogram fused, several key columns, a slot for missing paths), which serves the
+// aggregate route; this one is kept for its tests and as the baseline of
+// `bench_query.py --aggregate`.
 extern "C" __global__ void __launch_bounds__(kBlock)
 tt_group_count(const ColumnDesc* __restrict__ cols, int32_t g, const uint16_t* __restrict__ mask, int64_t nrows,
                int32_t ngroups, uint32_t* __restrict__ counts) {

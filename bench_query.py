@@ -11,6 +11,11 @@ in columnar form, then times the corrected overdue sweep
 program over the same narrow codes on every core of the process's CPU share
 (``ColumnarIndex.select_native``, AVX-512); ``--cpu`` adds the single-threaded NumPy reference.
 Reports rows scanned per second and effective HBM GB/s.
+
+``--aggregate`` is a benchmark of its own: the fused filter + histogram kernel
+(``ops/hip/group_agg.hip`` tt_scan_group) against the two-pass way to the same counts (scan to a
+selection mask + compaction, then ``tt_group_count`` over the mask), at three selectivities and
+three group cardinalities.
 """
 from __future__ import annotations
 
@@ -22,6 +27,90 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+
+def aggregate_bench(a) -> None:
+    """Nine points: a range filter selecting 1 %, 30 % and 100 % of the rows, grouped by a column
+    of 2 (2-bit codes), 200 (1 byte) and 100,000 (4 bytes) values.  The two methods alternate,
+    ``--reps`` rounds of ``--iters`` calls each after a warm-up of both; the median round counts,
+    the spread is the rounds' (max - min) / median.  Times are host clock around calls that end
+    in a device synchronise; both sides include allocating and zeroing their counters."""
+    import numpy as np
+    import torch
+
+    from aca_dotnet_workshop_amd.ops.columnar import OP_RANGE, TILE
+    from aca_dotnet_workshop_amd.ops.gpu import GpuKernels
+
+    k = GpuKernels("cuda:0")
+    dev = k.device
+    n = a.rows
+    cap = (n + TILE - 1) // TILE * TILE
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+
+    def column(card: int, width: int):
+        ids = torch.randint(0, card, (cap,), device=dev, generator=gen, dtype=torch.int32)
+        if width == 4:
+            return ids
+        if width == 1:
+            return ids.to(torch.uint8)
+        c = ids.to(torch.uint8).view(-1, 4)  # 2-bit codes, row r in bits 2(r mod 4) of byte r / 4
+        packed = c[:, 0] | (c[:, 1] << 2) | (c[:, 2] << 4) | (c[:, 3] << 6)
+        return torch.cat([packed, torch.zeros(16, dtype=torch.uint8, device=dev)])
+
+    groups = [(2, 0), (200, 1), (100_000, 4)]
+    tensors = [column(100, 1)] + [column(card, w) for card, w in groups]  # column 0: the filter's
+    table = torch.tensor([[t.data_ptr(), w] for t, w in zip(tensors, [1] + [w for _, w in groups])],
+                         dtype=torch.int64).to(dev)
+    live = torch.full((cap // 16,), -1, dtype=torch.int16, device=dev)  # rows < n live, 16 bits per word
+    live[(n + 15) // 16:] = 0
+    if n % 16:
+        live[n // 16] = (1 << (n % 16)) - 1
+    bitmaps = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def once(fn, iters: int) -> float:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+            torch.cuda.synchronize()  # as the caller, which reads the counters back after each
+        return (time.perf_counter() - t0) / iters
+
+    points = []
+    for pct in (1, 30, 100):
+        code = torch.tensor([[OP_RANGE, 0, 0, pct]], dtype=torch.int32).to(dev)  # ids 0 .. pct-1 of 100
+        for g, (card, w) in enumerate(groups, start=1):
+            def fused():
+                return k.scan_group(table, live, cap, n, code, bitmaps, [g], [card])
+
+            def two_pass():
+                _, mask = k.select(table, live, cap, n, code, bitmaps, return_mask=True)
+                return k.group_count(table, g, mask, n, card)
+            f, t = fused().cpu().numpy(), two_pass().cpu().numpy()
+            same = bool(np.array_equal(f[:card], t)) and int(f[card]) == 0
+            for _ in range(a.warmup):
+                fused(), two_pass()
+            rounds = [(once(fused, a.iters), once(two_pass, a.iters)) for _ in range(a.reps)]
+            fu, tp = (np.array([r[i] for r in rounds]) * 1e3 for i in (0, 1))
+            points.append({"selectivity_pct": pct, "groups": card, "selected": int(f.astype(np.int64).sum()),
+                           "fused_ms": round(float(np.median(fu)), 4), "two_pass_ms": round(float(np.median(tp)), 4),
+                           "fused_spread": round(float((fu.max() - fu.min()) / np.median(fu)), 3),
+                           "two_pass_spread": round(float((tp.max() - tp.min()) / np.median(tp)), 3),
+                           "counts_equal": same})
+    res = {"metric": "grouped_aggregate_fused_vs_two_pass", "rows": n, "iters": a.iters, "reps": a.reps,
+           "device": torch.cuda.get_device_name(0), "points": points}
+    if a.aggregate_out:
+        with open(a.aggregate_out, "w") as f:
+            f.write(f"# Fused scan + histogram against scan, compaction and group count\n\n"
+                    f"{res['device']}, {n:,} rows, median of {a.reps} rounds of {a.iters} calls, the two methods "
+                    f"alternating (`bench_query.py --aggregate`).\n\n"
+                    "| selected | groups | fused ms | two-pass ms | fused / two-pass | spread fused / two-pass | counts equal |\n"
+                    "|---|---|---|---|---|---|---|\n")
+            for p in points:
+                f.write(f"| {p['selectivity_pct']} % ({p['selected']:,}) | {p['groups']:,} | {p['fused_ms']:.4f} | "
+                        f"{p['two_pass_ms']:.4f} | {p['fused_ms'] / p['two_pass_ms']:.2f} | "
+                        f"{p['fused_spread']:.2f} / {p['two_pass_spread']:.2f} | {p['counts_equal']} |\n")
+    print(json.dumps(res), flush=True)
 
 
 def main() -> None:
@@ -38,7 +127,14 @@ def main() -> None:
                          "through the zone-map page path (hip/page_topk.hip)")
     ap.add_argument("--sorted", action="store_true",
                     help="also time ORDER BY taskDueDate DESC: top-100 page and full ordering (tt_sort_keys + sort)")
+    ap.add_argument("--aggregate", action="store_true",
+                    help="instead: the fused grouped-aggregate kernel against scan + group count, nine points")
+    ap.add_argument("--reps", type=int, default=5, help="--aggregate: alternating rounds per point")
+    ap.add_argument("--aggregate-out", default="", help="--aggregate: also write the table (markdown) here")
     a = ap.parse_args()
+    if a.aggregate:
+        aggregate_bench(a)
+        return
 
     import numpy as np
     import torch
