@@ -240,7 +240,7 @@ class CollectionAccelerator:
                 self.stats[key] = round(self.stats.get(key, 0.0) + v * 1e3, 3)
             _stall_note("accel-query", t2 - t_wait, lock_wait_ms=(t0 - t_wait) * 1e3, sync_ms=(t1 - t0) * 1e3,
                         select_ms=t_sel * 1e3, results_ms=t_res * 1e3)
-            for key, v in self.index.timing.items():  # the paged device path's own breakdown
+            for key, v in self.index.mirror.timing.items():  # the paged device path's own breakdown
                 self.stats[key] = round(v, 3)
             return out
 

@@ -21,15 +21,15 @@ import json
 import math
 import operator
 import os
-import time
-from dataclasses import dataclass
-from typing import Any, Iterable
+from dataclasses import dataclass, field
+from typing import Any, Iterable, NamedTuple
 
 import numpy as np
 
-OP_LEAF, OP_AND, OP_OR, OP_NOT, OP_TRUE, OP_EQ, OP_RANGE = 1, 2, 3, 4, 5, 6, 7
-TILE = 8192           # rows per kernel tile (ops/hip/query_scan.hip kTileRows)
-MAX_DEPTH = 8         # device stack depth (16-bit masks in a 128-bit register)
+from .codes import (MAX_DEPTH, OP_AND, OP_EQ, OP_LEAF, OP_NOT, OP_OR, OP_RANGE, OP_TRUE, TILE, col_bytes,
+                    encode_codes, gather, width_for)
+from .device_mirror import DeviceMirror
+
 _TYPE_ORDER = {type(None): 0, bool: 1, int: 2, float: 2, str: 3, list: 4, dict: 5}
 
 
@@ -628,7 +628,6 @@ class Column:
         return r
 
     def _general_ranks(self) -> np.ndarray:
-        import functools
         order = sorted(range(len(self.values)), key=functools.cmp_to_key(lambda a, b: compare(self.values[a], self.values[b])))
         r = np.empty(len(order), dtype=np.int64)
         rank = 0
@@ -644,9 +643,25 @@ class Program:
     code: np.ndarray      # [L, 4] int32
     bitmaps: np.ndarray   # int32 words (uint32 bit patterns)
     columns: list[int]
+    # its device copy, kept by DeviceMirror.program: ((rank slots, device), code, bitmaps)
+    device: Any = field(default=None, compare=False, repr=False)
+
+
+class SortField(NamedTuple):
+    """One sort key's field of the packed ordering key [rank(key0) | ... | seq]."""
+    col: int
+    ranks: np.ndarray   # dictionary id -> sort rank (int64)
+    missing: int        # rank of a missing path (it sorts like null)
+    max_rank: int       # a DESC key stores max_rank - rank
+    bits: int
+    desc: int
 
 
 class ColumnarIndex:
+    width_for = staticmethod(width_for)
+    col_bytes = staticmethod(col_bytes)
+
+
     def __init__(self, paths: Iterable[str] = (), capacity: int = TILE) -> None:
         self.columns: list[Column] = []
         self.col_of: dict[str, int] = {}
@@ -663,19 +678,18 @@ class ColumnarIndex:
         self._dead = 0      # tombstoned rows since the last compaction (upsert/delete path)
         self.n = 0
         self.version = 0
-        self._dev = None  # device mirror state
-        # compiled programs / device ordering plans, keyed by the query and the dictionaries'
-        # state (append-only dictionaries: sizes + rank versions identify their contents)
+        # compiled programs, keyed by the filter and the dictionaries' state (append-only
+        # dictionaries: sizes + rank versions identify their contents)
         self._prog_cache: dict[Any, Program] = {}
-        self._plan_cache: dict[Any, Any] = {}
         self._dict_gen = 0  # bumps when the dictionaries are rebuilt (re-encode from `source`)
-        self._tomb_dirty = False   # liveness changed for rows that are already on the device
-        self._full_dirty = True    # layout changed (compaction / new column / growth)
-        # zone maps of the paged device path, per sort spec (page_gpu): per tile the row with the
-        # smallest ordering key, re-computed for the tiles whose rows changed
-        self._zones: dict[Any, dict] = {}
-        self.timing: dict[str, float] = {}  # where the paged device path spends its time (summed)
-        self._plan_tm: dict[str, float] | None = None  # set while page_gpu plans (sub-step times)
+        self._host: dict | None = None  # the CPU scan's copies in the device layout (_host_mirror)
+        self._ncur = (0, 0, 0)  # native mirror cursor: (generation, rows seen, kill-log position)
+        # per column: native dictionary id -> this index's id, in a capacity-doubled buffer
+        # (``_remap_n`` entries used): a sync appends the new values' ids in place instead of
+        # copying the whole map (taskCreatedOn's grows by one per write)
+        self._remap: list[np.ndarray] = []
+        self._remap_n: list[int] = []
+        self.mirror = DeviceMirror(self)  # the GPU side: told what changes, synced by the queries
         for p in paths:
             self.add_column(p)
 
@@ -704,7 +718,7 @@ class ColumnarIndex:
             for j, text in enumerate(values):  # dictionary built by Python's own equality (vkey)
                 remap[j] = c.encode(json.loads(text))
             ids = np.asarray(ids, dtype=np.int32)
-            self.ids[i, :n] = np.where(ids >= 0, remap[np.maximum(ids, 0)] if remap.size else -1, -1)
+            self.ids[i, :n] = gather(remap, ids, -1)
             self.columns.append(c)
             self.col_of[path] = i
         self.live = np.zeros(cap, dtype=np.int32)
@@ -719,9 +733,8 @@ class ColumnarIndex:
         self._row_of = None  # built on the first write (read-only use never needs it)
         self.n = n
         self.version += 1
-        self._full_dirty = True
-        self._tomb_dirty = False
-        self._zones_reset()
+        self.mirror.invalidate()
+        self.mirror.reset_zones()
 
     # -- native mirror (DocStore column mirror, native/src/docstore.hpp) ---------------
     @classmethod
@@ -733,12 +746,6 @@ class ColumnarIndex:
         ix = cls()
         ix.native = store
         ix.docs = None
-        ix._ncur = (0, 0, 0)  # (generation, rows seen, kill-log position)
-        # per column: native dictionary id -> this index's id, in a capacity-doubled buffer
-        # (``_remap_n`` entries used): a sync appends the new values' ids in place instead of
-        # copying the whole map (taskCreatedOn's grows by one per write)
-        ix._remap: list[np.ndarray] = []
-        ix._remap_n: list[int] = []
         if not store.mirror_enable(list(dict.fromkeys(paths))):
             raise Unsupported("collection cannot be mirrored (TTL writes)")
         ix.sync()
@@ -765,7 +772,7 @@ class ColumnarIndex:
             self.seq = np.zeros(self.cap, dtype=np.int64)
             self.n, self._next_seq = 0, 0
             self._dict_gen += 1
-            self._full_dirty = True
+            self.mirror.invalidate()
             self.keys = []
         assert lo == self.n, (lo, self.n)
         self._grow(hi)
@@ -783,18 +790,18 @@ class ColumnarIndex:
                 self._remap_n[c] = need
             rm = self._remap[c][:self._remap_n[c]]
             if hi > lo:
-                self.ids[c, lo:hi] = np.where(ids >= 0, rm[np.maximum(ids, 0)] if rm.size else -1, -1)
+                self.ids[c, lo:hi] = gather(rm, ids, -1)
         if hi > lo:
             self.seq[lo:hi] = d["seqs"]
             self.live[lo:hi] = d["live"]
             self._next_seq = max(self._next_seq, int(d["seqs"].max()))
-            self._zones_touch(np.arange(lo // TILE, (hi - 1) // TILE + 1))
+            self.mirror.touch(np.arange(lo // TILE, (hi - 1) // TILE + 1))
         if d["kills"].size:
             self.live[d["kills"].astype(np.int64)] = 0
-            self._tomb_dirty = True
-            self._zones_touch(np.unique(d["kills"].astype(np.int64) // TILE))
+            self.mirror.tombstoned()
+            self.mirror.touch(np.unique(d["kills"].astype(np.int64) // TILE))
         if d["full"]:
-            self._zones_reset()
+            self.mirror.reset_zones()
         self.n = hi
         self._ncur = (int(d["gen"]), hi, int(d["kill_cursor"]))
         if changed:
@@ -804,7 +811,7 @@ class ColumnarIndex:
     @property
     def generation(self) -> int:
         """Mirror generation the row numbers belong to (``DocStore.mirror_results`` checks it)."""
-        return int(self._ncur[0]) if getattr(self, "native", None) is not None else 0
+        return int(self._ncur[0]) if self.native is not None else 0
 
     @property
     def row_of(self) -> dict[str, int]:
@@ -817,7 +824,7 @@ class ColumnarIndex:
         missing = [p for p in dict.fromkeys(paths) if p not in self.col_of]
         if not missing:
             return
-        if getattr(self, "native", None) is not None:
+        if self.native is not None:
             if not self.native.mirror_enable([c.path for c in self.columns] + missing):
                 raise Unsupported("collection mirror disabled (TTL writes)")
             self.sync()  # a new column is a new mirror generation: full reload
@@ -826,16 +833,6 @@ class ColumnarIndex:
         else:
             for p in missing:
                 self.add_column(p)
-
-    # -- zone maps (paged device path) ---------------------------------------------------
-    def _zones_touch(self, tiles) -> None:
-        for z in self._zones.values():
-            if not z["all"]:
-                z["dirty"].update(int(t) for t in tiles)
-
-    def _zones_reset(self) -> None:
-        for z in self._zones.values():
-            z["all"], z["dirty"] = True, set()
 
     # -- maintenance ----------------------------------------------------------
     def add_column(self, path: str) -> int:
@@ -854,7 +851,7 @@ class ColumnarIndex:
                 col[0, r] = c.encode(get_path(self.docs[r], path))
         self.ids = np.concatenate([self.ids, col], axis=0)
         self.version += 1
-        self._full_dirty = True
+        self.mirror.invalidate()
         return idx
 
     def _grow(self, need: int) -> None:
@@ -870,7 +867,7 @@ class ColumnarIndex:
         seq = np.zeros(cap, dtype=np.int64)
         seq[:self.n] = self.seq[:self.n]
         self.ids, self.live, self.seq, self.cap = ids, live, seq, cap
-        self._full_dirty = True
+        self.mirror.invalidate()
 
     def upsert(self, key: str, doc: Any) -> None:
         old = self.row_of.get(key)
@@ -878,7 +875,7 @@ class ColumnarIndex:
             self.live[old] = 0
             if self.docs is not None:
                 self.docs[old] = None
-            self._tomb_dirty = True
+            self.mirror.tombstoned()
             self._dead += 1
             seq = int(self.seq[old])  # an update keeps the key's original position (native engine semantics)
         else:
@@ -896,7 +893,7 @@ class ColumnarIndex:
         self.row_of[key] = r
         self.n += 1
         self.version += 1
-        self._zones_touch([r // TILE] if old is None else [r // TILE, old // TILE])
+        self.mirror.touch([r // TILE] if old is None else [r // TILE, old // TILE])
         self._maybe_compact()
 
     def delete(self, key: str) -> None:
@@ -905,10 +902,10 @@ class ColumnarIndex:
             self.live[r] = 0
             if self.docs is not None:
                 self.docs[r] = None
-            self._tomb_dirty = True
+            self.mirror.tombstoned()
             self._dead += 1
             self.version += 1
-            self._zones_touch([r // TILE])
+            self.mirror.touch([r // TILE])
         self._maybe_compact()
 
     def _maybe_compact(self) -> None:
@@ -938,8 +935,8 @@ class ColumnarIndex:
         self.n = len(keep)
         self._dead = 0
         self.version += 1
-        self._full_dirty = True
-        self._zones_reset()
+        self.mirror.invalidate()
+        self.mirror.reset_zones()
 
     # -- compilation ---------------------------------------------------------
     def _dict_state(self) -> tuple:
@@ -1055,9 +1052,7 @@ class ColumnarIndex:
             if op == OP_EQ:
                 stack.append(self.ids[a, :n] == b)
             elif op == OP_RANGE:
-                v = self.ids[a, :n]
-                ranks = self.columns[a].ranks()
-                r = np.where(v >= 0, ranks[np.maximum(v, 0)] if ranks.size else -1, -1)
+                r = gather(self.columns[a].ranks(), self.ids[a, :n], -1)
                 stack.append((r >= b) & (r < c))
             elif op == OP_LEAF:
                 v = self.ids[a, :n]
@@ -1098,13 +1093,13 @@ class ColumnarIndex:
         """Host copies of the columns in the device layout (narrow codes, rank-encoded copies for
         the program's range leaves, 1-bit liveness), rebuilt when the index changed."""
         key = (self.version, self.n, self.cap, self._dict_state())
-        hm = getattr(self, "_host", None)
+        hm = self._host
         if hm is None or hm["key"] != key:
-            widths = [self.width_for(len(c.values)) for c in self.columns]
+            widths = [width_for(len(c.values)) for c in self.columns]
             hm = self._host = {"key": key, "widths": widths, "ranks": {},
-                               "cols": [(np.ascontiguousarray(self._narrow(i, 0, self.cap, w)).view(np.uint8), w)
+                               "cols": [(np.ascontiguousarray(self.codes(i, 0, self.cap, w)).view(np.uint8), w)
                                         for i, w in enumerate(widths)],
-                               "live": np.ascontiguousarray(self._live_words(0, self.cap // 16)).view(np.uint16)}
+                               "live": np.ascontiguousarray(self.live_words(0, self.cap // 16)).view(np.uint16)}
         rank_cols = sorted(set(prog.code[prog.code[:, 0] == OP_RANGE, 1].tolist()))
         slots = {}
         cols = list(hm["cols"][:len(self.columns)])
@@ -1112,179 +1107,25 @@ class ColumnarIndex:
             r = hm["ranks"].get(col)
             if r is None:
                 w = max(1, hm["widths"][col])
-                table = self.columns[col].ranks()
-                v = self.ids[col, :self.cap]
-                rk = np.where(v >= 0, table[np.maximum(v, 0)] if table.size else -1, -1)
-                dt = np.uint8 if w == 1 else np.uint16 if w == 2 else np.int32
-                rk = np.where(rk < 0, np.iinfo(dt).max if w < 4 else -1, rk).astype(dt)
+                rk = encode_codes(gather(self.columns[col].ranks(), self.ids[col, :self.cap], -1), w)
                 r = hm["ranks"][col] = (np.ascontiguousarray(rk).view(np.uint8), w)
             slots[col] = len(cols)
             cols.append(r)
         return {"cols": cols, "live": hm["live"], "rank_slot": slots}
 
-    # device mirror -------------------------------------------------------------
-    @staticmethod
-    def width_for(dict_size: int) -> int:
-        """Code width of a column whose dictionary has ``dict_size`` ids (all-ones = missing):
-        0 = 2 bits per row (<= 3 ids: booleans, with or without null), else bytes per row."""
-        return 0 if dict_size <= 3 else 1 if dict_size <= 254 else 2 if dict_size <= 65534 else 4
+    def codes(self, col: int, lo: int, hi: int, width: int) -> np.ndarray:
+        """Codes of rows [lo, hi) of a column in the device layout (width 0: ``lo``/``hi``
+        multiples of 4)."""
+        return encode_codes(self.ids[col, lo:hi], width)
 
-    @staticmethod
-    def col_bytes(rows: int, width: int) -> int:
-        return rows // 4 if width == 0 else rows * width
-
-    def _narrow(self, col: int, lo: int, hi: int, width: int) -> np.ndarray:
-        """Codes of rows [lo, hi) in the device layout (width 0: ``lo``/``hi`` multiples of 4,
-        four rows per byte, row r in bits 2(r mod 4))."""
-        v = self.ids[col, lo:hi]
-        if width == 4:
-            return v
-        if width == 0:
-            c = np.where(v < 0, 3, v).astype(np.uint8).reshape(-1, 4)
-            return c[:, 0] | (c[:, 1] << 2) | (c[:, 2] << 4) | (c[:, 3] << 6)
-        dt = np.uint8 if width == 1 else np.uint16
-        return np.where(v < 0, np.iinfo(dt).max, v).astype(dt)
-
-    def _device_codes(self, col: int, width: int) -> np.ndarray:
-        """The whole column in the device layout; 2-bit columns get 16 bytes of padding (the
-        reads past the end of a partial group stay inside the buffer)."""
-        v = self._narrow(col, 0, self.cap, width)
-        if width == 0:
-            v = np.concatenate([v, np.zeros(16, dtype=np.uint8)])
-        return np.ascontiguousarray(v)
-
-    def _live_words(self, lo_word: int, hi_word: int) -> np.ndarray:
+    def live_words(self, lo_word: int, hi_word: int) -> np.ndarray:
+        """Liveness of rows [16 lo_word, 16 hi_word), one bit per row."""
         bits = self.live[lo_word * 16:hi_word * 16].astype(np.uint8)
         return np.packbits(bits, bitorder="little").view("<u2").view(np.int16)
 
-    def to_device(self, kernels, rank_cols=()):
-        """Sync the device mirror.  Columns are append-only between compactions, so only rows
-        added since the last sync are uploaded; tombstones re-upload the 1-bit liveness mask
-        (N/8 bytes); a column whose dictionary outgrows its width is re-encoded."""
-        torch = kernels.torch
-        dev = kernels.device
-        st = self._dev
-        widths = [self.width_for(len(c.values)) for c in self.columns]
-        nwords = self.cap // 16
-        if st is None or self._full_dirty or st["cap"] != self.cap or len(st["cols"]) != len(self.columns):
-            if self._full_dirty:
-                self._zones_reset()
-            cols = [torch.from_numpy(self._device_codes(i, w)).to(dev) for i, w in enumerate(widths)]
-            live = torch.from_numpy(self._live_words(0, nwords)).to(dev)
-            seq = torch.from_numpy(self.seq[:self.cap].astype(np.int32)).to(dev)  # uint32 on device
-            st = self._dev = {"cols": cols, "widths": widths, "live": live, "synced": self.n, "cap": self.cap,
-                              "seq": seq}
-        else:
-            lo, hi = st["synced"], self.n
-            # the appended rows of every column, the sequence and the liveness words go up in
-            # one scatter launch (GpuKernels.upload), not one copy each
-            segs = []
-            for i, w in enumerate(widths):
-                if w != st["widths"][i]:
-                    st["cols"][i] = torch.from_numpy(self._device_codes(i, w)).to(dev)
-                    st["widths"][i] = w
-                elif hi > lo and w == 0:  # whole bytes of 4 rows: re-pack the edge bytes
-                    a, b = lo // 4, (hi + 3) // 4
-                    segs.append((st["cols"][i].data_ptr() + a, self._narrow(i, 4 * a, 4 * b, 0)))
-                elif hi > lo:
-                    segs.append((st["cols"][i].data_ptr() + lo * w, self._narrow(i, lo, hi, w)))
-            if hi > lo:
-                segs.append((st["seq"].data_ptr() + 4 * lo, self.seq[lo:hi].astype(np.int32)))
-            if self._tomb_dirty:
-                segs.append((st["live"].data_ptr(), self._live_words(0, nwords)))
-            elif hi > lo:
-                w0, w1 = lo // 16, (hi + 15) // 16
-                segs.append((st["live"].data_ptr() + 2 * w0, self._live_words(w0, w1)))
-            kernels.upload(segs)
-            st["synced"] = hi
-        self._full_dirty = False
-        self._tomb_dirty = False
-        rows = [[c.data_ptr(), w] for c, w in zip(st["cols"], st["widths"])]
-        if rank_cols:
-            # rank-encoded copies of the columns that range leaves read (appended to the table)
-            ranks = st.setdefault("ranks", {})
-            slot = {}
-            for col in sorted(set(rank_cols)):
-                self._sync_rank_column(kernels, st, ranks, col)
-                slot[col] = len(rows)
-                rows.append([ranks[col]["t"].data_ptr(), ranks[col]["w"]])
-            st["rank_slot"] = slot
-        # the descriptor table only changes with the device buffers: no upload per query
-        st["table_widths"] = np.array([w for _, w in rows], dtype=np.int64)
-        tkey = tuple(tuple(r) for r in rows)
-        tables = st.setdefault("tables", {})
-        t = tables.get(tkey)
-        if t is None:
-            if len(tables) >= 16:
-                tables.clear()
-            t = tables[tkey] = torch.from_numpy(np.array(rows, dtype=np.int64).reshape(-1, 2)).to(dev)
-        st["table"] = t
-        return st
-
-    def _sync_rank_column(self, kernels, st, ranks, col: int) -> None:
-        torch = kernels.torch
-        c = self.columns[col]
-        w = max(1, st["widths"][col])  # ranks run 1..n and need a distinct missing code: >= 1 byte
-        cur = ranks.get(col)
-        full = cur is None or cur["w"] != w or cur["ver"] != c.rank_version
-        lo = 0 if full else cur["synced"]
-        if not full and lo >= self.n:
-            return
-        segs = []  # the rank table and the source descriptor: one scatter launch, no copies
-        if full:
-            dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[w]
-            prev = cur
-            # re-encoded from row 0 into the same buffer when it still fits: its address is in
-            # the column descriptor table, which then needs no new upload
-            keep = prev is not None and prev["w"] == w and prev["t"].numel() == self.cap
-            cur = ranks[col] = {"t": prev["t"] if keep else torch.empty(self.cap, dtype=dt, device=kernels.device),
-                                "w": w, "ver": c.rank_version, "table": None, "synced": 0}
-            table = c.ranks().astype(np.int32) if c.values else np.zeros(1, dtype=np.int32)
-            # a new dictionary value re-ranks the column (every new due date does): the table's
-            # device buffer is kept across versions and grown by doubling
-            buf = prev.get("table_buf") if prev is not None else None
-            if buf is None or buf.numel() < table.size:
-                buf = torch.empty(max(1024, 1 << (table.size - 1).bit_length()), dtype=torch.int32,
-                                  device=kernels.device)
-            cur["table_buf"], cur["table"] = buf, buf[:table.size]
-            segs.append((buf.data_ptr(), table))
-            if prev is not None and "src" in prev:
-                cur["src"], cur["src_key"] = prev["src"], prev["src_key"]
-        key = (st["cols"][col].data_ptr(), st["widths"][col])
-        if cur.get("src_key") != key:  # the source column's descriptor: uploaded when it changes
-            if "src" not in cur:
-                cur["src"] = torch.empty((1, 2), dtype=torch.int64, device=kernels.device)
-            segs.append((cur["src"].data_ptr(), np.array([list(key)], dtype=np.int64)))
-            cur["src_key"] = key
-        kernels.upload(segs)
-        kernels.rank_encode(cur["src"], cur["table"], lo, self.n, cur["t"], w)
-        cur["synced"] = self.n
-
-    def device_program(self, prog: Program, kernels):
-        """Sync the device mirror for ``prog`` and return (state, program, bitmaps) ready for
-        ``GpuKernels.select`` (range leaves remapped to their rank-encoded columns)."""
-        leaf = (prog.code[:, 0] == OP_LEAF) | (prog.code[:, 0] == OP_EQ) | (prog.code[:, 0] == OP_RANGE)
-        if leaf.any() and int(prog.code[leaf, 1].max()) >= len(self.columns):
-            raise ValueError("program references a column outside the index")
-        rng = prog.code[:, 0] == OP_RANGE
-        self._warm_rank_cols = prog.code[rng, 1].tolist()
-        st = self.to_device(kernels, self._warm_rank_cols)
-        slots = tuple(sorted(st.get("rank_slot", {}).items())) if rng.any() else ()
-        cached = getattr(prog, "_dev", None)
-        if cached is not None and cached[0] == (slots, str(kernels.device)):
-            return st, cached[1], cached[2]
-        code_np = prog.code
-        if rng.any():  # range leaves read the rank-encoded copy of their column
-            code_np = prog.code.copy()
-            code_np[rng, 1] = [st["rank_slot"][c] for c in prog.code[rng, 1].tolist()]
-        code = kernels.torch.from_numpy(code_np).to(kernels.device)
-        bitmaps = kernels.torch.from_numpy(prog.bitmaps).to(kernels.device)
-        prog._dev = ((slots, str(kernels.device)), code, bitmaps)  # reused while the program is
-        return st, code, bitmaps
-
+    # -- on the GPU (device_mirror.py keeps the device side) ---------------------------------
     def select_gpu(self, prog: Program, kernels, return_mask: bool = False, on_device: bool = False):
-        st, code, bitmaps = self.device_program(prog, kernels)
-        res = kernels.select(st["table"], st["live"], self.cap, self.n, code, bitmaps, return_mask=return_mask)
+        res = self.mirror.select(prog, kernels, return_mask)
         if return_mask or on_device:
             return res
         return res.cpu().numpy()
@@ -1295,7 +1136,7 @@ class ColumnarIndex:
         col = self.columns[g]
         if mask is None or not col.values:
             return {}
-        counts = kernels.group_count(self._dev["table"], g, mask, self.n, len(col.values)).cpu().numpy()
+        counts = kernels.group_count(self.mirror.table, g, mask, self.n, len(col.values)).cpu().numpy()
         return {json.dumps(col.values[i]): int(x) for i, x in enumerate(counts) if x}
 
     def group_count_numpy(self, prog: Program, group_path: str) -> dict[str, int]:
@@ -1327,8 +1168,7 @@ class ColumnarIndex:
         gcols = [self.col_of[p] for p in spec.group_by]
         dev = None
         if kernels is not None:
-            st, code, bitmaps = self.device_program(prog, kernels)
-            dev = (st, code, bitmaps, int(kernels.lib.tt_group_max_cells()))
+            dev = (*self.mirror.program(prog, kernels), int(kernels.lib.tt_group_max_cells()))
         host_rows: list[np.ndarray] = []  # the CPU selection, made once when a histogram needs it
 
         def histogram(cols: list[int]) -> tuple[np.ndarray, np.ndarray, list[int]]:
@@ -1338,7 +1178,7 @@ class ColumnarIndex:
             if ncells >= 1 << 62:
                 raise Unsupported("aggregate key space too large")
             if dev is not None and ncells <= dev[3]:
-                counts = kernels.scan_group(dev[0]["table"], dev[0]["live"], self.cap, self.n, dev[1], dev[2],
+                counts = kernels.scan_group(dev[0].table, dev[0].live, self.cap, self.n, dev[1], dev[2],
                                             cols, dims).cpu().numpy().view(np.uint32)
                 cells = np.nonzero(counts)[0]
                 return cells, counts[cells], dims
@@ -1408,39 +1248,39 @@ class ColumnarIndex:
         if not sort:
             return rows
         keys = []
-        for s in reversed(sort):  # np.lexsort: last key is primary
-            col = self.add_column(s["key"])
-            ranks = self.columns[col].ranks()
-            ids = self.ids[col, rows]
-            miss = self.columns[col].missing_rank()
-            r = np.where(ids >= 0, ranks[np.maximum(ids, 0)] if ranks.size else miss, miss)
-            if str(s.get("order", "ASC")).upper() == "DESC":
-                r = -r
-            keys.append(r)
+        for f in reversed(self.sort_fields(sort)[0]):  # np.lexsort: last key is primary
+            r = gather(f.ranks, self.ids[f.col, rows], f.missing)
+            keys.append(-r if f.desc else r)
         return rows[np.lexsort(keys)]
+
+    def sort_fields(self, sort: list[dict[str, Any]] | None) -> tuple[list[SortField], int]:
+        """The packed ordering key [rank(key0) | ... | seq] of ``sort``: its fields, primary first,
+        and the bits of the sequence tail -- for ``sort_specs``, ``DeviceMirror.sort_plan`` and
+        ``order_lexsort`` alike."""
+        fields = []
+        for s in sort or []:
+            col = self.add_column(s["key"])
+            c = self.columns[col]
+            ranks = c.ranks() if c.values else np.zeros(0, dtype=np.int64)
+            miss = c.missing_rank()
+            # a string-only dictionary's ranks are exactly 1..n: no O(dictionary) max per query
+            max_rank = max(len(c.values) if c.str_only else int(ranks.max(initial=0)), miss)
+            desc = int(str(s.get("order", "ASC")).upper() == "DESC")
+            fields.append(SortField(col, ranks, miss, max_rank, max(1, max_rank.bit_length()), desc))
+        # every seq is <= the last one handed out
+        return fields, max(1, int(self._next_seq).bit_length())
 
     def sort_specs(self, sort: list[dict[str, Any]] | None) -> tuple[np.ndarray, np.ndarray, int] | None:
         """Device ordering plan: (specs int32 [nkeys, 8], concatenated rank tables, seq bits), or
         None when the packed key would not fit 63 bits (the host path orders instead)."""
-        seq_bits = max(1, int(self._next_seq).bit_length())  # every seq is <= the last one handed out
-        specs, tables, off, total = [], [], 0, seq_bits
-        for s in sort or []:
-            col = self.add_column(s["key"])
-            c = self.columns[col]
-            ranks = c.ranks().astype(np.int32) if c.values else np.zeros(0, dtype=np.int32)
-            miss = c.missing_rank()
-            max_rank = int(max(int(ranks.max(initial=0)), miss))
-            bits = max(1, max_rank.bit_length())
-            total += bits
-            desc = 1 if str(s.get("order", "ASC")).upper() == "DESC" else 0
-            specs.append([col, off, ranks.size, bits, desc, miss, max_rank, 0])
-            tables.append(ranks)
-            off += ranks.size
-        if total > 63:
+        fields, seq_bits = self.sort_fields(sort)
+        if seq_bits + sum(f.bits for f in fields) > 63:
             return None
-        spec_arr = np.array(specs, dtype=np.int32).reshape(-1, 8)
-        rank_arr = np.concatenate(tables) if tables else np.zeros(1, dtype=np.int32)
-        return spec_arr, (rank_arr if rank_arr.size else np.zeros(1, dtype=np.int32)), seq_bits
+        offs = np.cumsum([0] + [f.ranks.size for f in fields])
+        specs = [[f.col, int(off), f.ranks.size, f.bits, f.desc, f.missing, f.max_rank, 0]
+                 for f, off in zip(fields, offs)]
+        tables = [f.ranks.astype(np.int32) for f in fields if f.ranks.size] or [np.zeros(1, dtype=np.int32)]
+        return np.array(specs, dtype=np.int32).reshape(-1, 8), np.concatenate(tables), seq_bits
 
     def sort_keys_numpy(self, rows: np.ndarray, plan) -> np.ndarray:
         """Host reference of ``hip/sort_keys.hip``: the packed ordering key of every row."""
@@ -1456,220 +1296,17 @@ class ColumnarIndex:
             k = (k << bits) | r
         return (k << seq_bits) | self.seq[rows]
 
-    def _device_sort_plan(self, sort, kernels):
-        """(specs, rank tables, seq bits, key bits) on the device and the host plan of the same
-        packed key, kept per sort spec; None when the device cannot order by it (too many keys,
-        a key over 63 bits, a sequence over 32 bits).
-
-        The rank tables live in one buffer, one capacity-doubled region per sort key, on the
-        device and (for ``sort_keys_numpy``) on the host.  Only the ids whose rank is new or moved
-        since the last query are copied (``Column.rank_changes_since``): for the timestamps of
-        new writes, which arrive nearly in order, those are the newest ids -- O(new values) per
-        query instead of re-uploading the whole table (``taskCreatedOn`` has one value per
-        task)."""
-        if len(sort or []) > kernels.max_sort_keys:
-            return None
-        tm = self._plan_tm  # page_gpu's timing dict while it plans (None for the background warm)
-        c0 = time.thread_time()
-        cols = [self.add_column(srt["key"]) for srt in sort or []]
-        seq_bits = max(1, int(self._next_seq).bit_length())
-        if seq_bits > 32:
-            return None  # the device keeps a 32-bit insertion sequence
-        torch = kernels.torch
-        pkey = (json.dumps(sort, sort_keys=True, default=str), str(kernels.device), self._dict_gen)
-        ent = self._plan_cache.get(pkey)
-        tables, specs_rows, total = [], [], seq_bits
-        for srt, col in zip(sort or [], cols):
-            c = self.columns[col]
-            r = c.ranks() if c.values else np.zeros(0, dtype=np.int64)
-            miss = c.missing_rank()
-            max_rank = len(c.values) if c.str_only else int(r.max(initial=0))
-            max_rank = max(max_rank, miss)
-            bits = max(1, max_rank.bit_length())
-            total += bits
-            desc = 1 if str(srt.get("order", "ASC")).upper() == "DESC" else 0
-            tables.append((r, c))
-            specs_rows.append([col, 0, r.size, bits, desc, miss, max_rank, 0])
-        if total > 63:
-            return None
-        los = [None] * len(tables) if ent is None else \
-            [c.rank_changes_since(sq) for (_, c), sq in zip(tables, ent["seqs"])]
-        rebuild = ent is None or any(lo is None for lo in los) or \
-            any(r.size > cap for (r, _), cap in zip(tables, ent["caps"]))
-        c1 = time.thread_time()
-        if tm is not None:
-            tm["plan_ranks_ms"] = tm.get("plan_ranks_ms", 0.0) + (c1 - c0) * 1e3
-            tm["plan_rebuilds"] = tm.get("plan_rebuilds", 0) + int(rebuild)
-        if rebuild:
-            caps = [max(1024, 1 << max(0, int(r.size * 1.25) + 1).bit_length()) for r, _ in tables]
-            offs = np.concatenate([[0], np.cumsum(caps)[:-1]]).astype(np.int64) if caps else np.zeros(0, np.int64)
-            host = np.zeros(max(1, int(sum(caps))), dtype=np.int32)
-            for (r, _), off in zip(tables, offs):
-                host[off:off + r.size] = r
-            ent = {"caps": caps, "offs": offs, "seqs": [c.rank_seq for _, c in tables],
-                   "host": host, "dev": torch.from_numpy(host).to(kernels.device), "specs": None,
-                   "specs_dev": torch.empty((len(specs_rows), 8), dtype=torch.int32, device=kernels.device)}
-            if len(self._plan_cache) >= 64:
-                self._plan_cache.pop(next(iter(self._plan_cache)))
-            self._plan_cache[pkey] = ent
-        segs = []  # rank tails and the spec rows: one scatter launch (ops/gpu.py upload)
-        if not rebuild:
-            for i, ((r, c), lo) in enumerate(zip(tables, los)):
-                off = int(ent["offs"][i])
-                if r.size > lo:  # the ids whose rank is new or moved (the newest ones)
-                    tail = r[lo:].astype(np.int32)
-                    ent["host"][off + lo:off + r.size] = tail
-                    segs.append((ent["dev"].data_ptr() + 4 * (off + lo), tail))
-                ent["seqs"][i] = c.rank_seq
-        for row, off in zip(specs_rows, ent["offs"]):
-            row[1] = int(off)
-        specs = np.array(specs_rows, dtype=np.int32).reshape(-1, 8)
-        if ent["specs"] is None or not np.array_equal(specs, ent["specs"]):
-            # the spec rows change with every new dictionary value (row[2] is the table's size):
-            # they ride the same launch into a buffer allocated once per plan
-            ent["specs"] = specs
-            segs.append((ent["specs_dev"].data_ptr(), specs))
-        c2 = time.thread_time()
-        kernels.upload(segs)
-        if tm is not None:
-            c3 = time.thread_time()
-            tm["plan_tails_ms"] = tm.get("plan_tails_ms", 0.0) + (c2 - c1) * 1e3
-            tm["plan_upload_ms"] = tm.get("plan_upload_ms", 0.0) + (c3 - c2) * 1e3
-            tm["plan_tail_rows"] = tm.get("plan_tail_rows", 0) + sum(int(t.size) for _, t in segs)
-        key_bits = seq_bits + int(specs[:, 3].sum()) if specs.size else seq_bits
-        return ent["specs_dev"], ent["dev"], seq_bits, key_bits, (specs, ent["host"], seq_bits)
-
     def order_gpu(self, rows, sort, kernels, k: int | None = None):
-        """Order a device selection on the GPU (``hip/sort_keys.hip`` + radix sort / top-k);
-        returns device rows, or None when the host path must order."""
-        hit = self._device_sort_plan(sort, kernels)
-        if hit is None:
-            return None
-        specs_t, ranks_t, seq_bits, key_bits, _ = hit
-        st = self.to_device(kernels)  # sort keys may have added columns
-        return kernels.order(st["table"], rows, specs_t, ranks_t, st["seq"], seq_bits, k, key_bits)
-
-    def _zone_refresh(self, z: dict, kernels, st: dict, specs_t, ranks_t, seq_bits: int) -> None:
-        """Recompute the zone argmin of the tiles that changed since the last refresh."""
-        ntiles = (self.n + TILE - 1) // TILE
-        if z["zarg"].size < ntiles:  # new tiles: not computed yet
-            z["dirty"].update(range(z["zarg"].size, ntiles))
-            z["zarg"] = np.concatenate([z["zarg"], np.full(ntiles - z["zarg"].size, -1, dtype=np.int32)])
-        z["zarg"] = z["zarg"][:ntiles]
-        todo = np.arange(ntiles, dtype=np.int32) if z["all"] else \
-            np.fromiter((t for t in z["dirty"] if t < ntiles), dtype=np.int32)
-        if todo.size:
-            z["zarg"][todo] = kernels.zone_argmin(st["table"], st["live"], self.n, specs_t, ranks_t, st["seq"],
-                                                  seq_bits, todo)
-        z["all"], z["dirty"] = False, set()
+        """Order a device selection on the GPU; device rows, or None when the host must order."""
+        return self.mirror.order(rows, sort, kernels, k)
 
     def warm(self, kernels) -> None:
-        """Bring the device mirror up to the host index between queries: upload the rows
-        synced since the last query (with the rank-encoded columns the last queries read) and
-        refresh the zone maps of the sorts already served, so a query finds little to do.
-        Called by the accelerator's background sync (backing/accel.py) under its lock."""
-        st = self.to_device(kernels, getattr(self, "_warm_rank_cols", ()))
-        for z in list(self._zones.values()):
-            if z["all"] or z["dirty"] or z["zarg"].size < (self.n + TILE - 1) // TILE:
-                hit = self._device_sort_plan(z["sort"], kernels)
-                if hit is not None:
-                    self._zone_refresh(z, kernels, st, hit[0], hit[1], hit[2])
+        """Called by the accelerator's background sync (backing/accel.py) under its lock."""
+        self.mirror.warm(kernels)
 
     def page_gpu(self, prog: Program, sort, kernels, offset: int, limit: int):
-        """A page [offset, offset + limit) of an ordered query without scanning the collection
-        (``hip/page_topk.hip``): zone maps pick the tiles that can hold the page, only those are
-        evaluated, one workgroup orders the candidates.  Returns (rows, token) or None when the
-        page does not fit the device top-k (the caller takes the full path)."""
-        k_total = offset + limit
-        if limit <= 0 or k_total > kernels.page_cap:
-            return None
-        tm = self.timing
-        t0, c0 = time.perf_counter(), time.thread_time()
-        self._plan_tm = tm
-        try:
-            hit = self._device_sort_plan(sort, kernels)
-        finally:
-            self._plan_tm = None
-        if hit is None:
-            return None
-        specs_t, ranks_t, seq_bits, _, plan = hit
-        t1 = time.perf_counter()
-        st, code, bitmaps = self.device_program(prog, kernels)
-        t2, c2 = time.perf_counter(), time.thread_time()
-        tm["page_plan_ms"] = tm.get("page_plan_ms", 0.0) + (t1 - t0) * 1e3
-        tm["page_program_ms"] = tm.get("page_program_ms", 0.0) + (t2 - t1) * 1e3
-        # this thread's CPU time in plan + program: the wall time above less the waits (GIL,
-        # other threads on the core)
-        tm["page_host_cpu_ms"] = tm.get("page_host_cpu_ms", 0.0) + (c2 - c0) * 1e3
-        ntiles = (self.n + TILE - 1) // TILE
-        if ntiles == 0:
-            return np.zeros(0, dtype=np.int32), None
-        zkey = json.dumps(sort, sort_keys=True, default=str)
-        z = self._zones.get(zkey)
-        if z is None:
-            z = self._zones[zkey] = {"zarg": np.zeros(0, dtype=np.int32), "dirty": set(), "all": True, "density": {},
-                                     "sort": sort}
-        self._zone_refresh(z, kernels, st, specs_t, ranks_t, seq_bits)
-        t3 = time.perf_counter()
-        tm["page_zones_ms"] = tm.get("page_zones_ms", 0.0) + (t3 - t2) * 1e3
-        zarg = z["zarg"]
-        valid = zarg >= 0
-        nvalid = int(valid.sum())
-        if nvalid == 0:
-            return np.zeros(0, dtype=np.int32), None
-        top = np.iinfo(np.uint64).max
-        keys = np.full(ntiles, top, dtype=np.uint64)
-        keys[valid] = self.sort_keys_numpy(zarg[valid], plan).astype(np.uint64)
-        pkey = (prog.code.tobytes(), prog.bitmaps.tobytes())
-        dens = z["density"].get(pkey, 0.25)  # candidates per row of a chosen tile, from the last page
-        b = min(nvalid, max(1, int(np.ceil(1.5 * k_total / max(dens * TILE, 1.0)))))
-        if z.setdefault("short", {}).get(pkey):
-            # the last page of this filter held every match in the collection (fewer than the
-            # page): start from every tile instead of growing towards it one launch at a time
-            b = nvalid
-        lo_b, hi_b = 0, None  # largest tile count seen short of k candidates / smallest that overflowed
-        launches = 0
-        for _ in range(24):
-            if b >= nvalid:
-                chosen, bound = np.nonzero(valid)[0].astype(np.int32), top
-            else:
-                part = np.argpartition(keys, b)
-                chosen, bound = part[:b].astype(np.int32), int(keys[part[b]])
-            rows, total, complete = kernels.page(st["table"], st["live"], self.n, code, bitmaps, specs_t, ranks_t,
-                                                 st["seq"], seq_bits, chosen, k_total, offset, bound)
-            launches += 1
-            if complete:
-                break
-            if total > kernels.page_cap:  # more candidates than one workgroup sorts: fewer tiles
-                hi_b = b
-            else:
-                lo_b = b
-            if hi_b is None:
-                b = min(nvalid, b * 4)
-            elif hi_b - lo_b <= 1:
-                return None  # no tile count gives k candidates the LDS sort holds
-            else:
-                b = (lo_b + hi_b) // 2
-        else:
-            return None
-        if len(chosen):
-            z["density"][pkey] = max(total / (len(chosen) * TILE), 1e-4)
-            if len(z["density"]) > 64:
-                z["density"].pop(next(iter(z["density"])))
-        z["short"][pkey] = bound == top and total < k_total
-        if len(z["short"]) > 64:
-            z["short"].pop(next(iter(z["short"])))
-        t4 = time.perf_counter()
-        tm["page_kernels_ms"] = tm.get("page_kernels_ms", 0.0) + (t4 - t3) * 1e3
-        tm["page_launches"] = tm.get("page_launches", 0) + launches
-        if total > k_total:
-            more = True
-        elif bound == top:
-            more = False
-        else:  # the page used every candidate: are there matches in the tiles left out?
-            more = int(self.select_gpu(prog, kernels, on_device=True).numel()) > k_total
-            tm["page_more_ms"] = tm.get("page_more_ms", 0.0) + (time.perf_counter() - t4) * 1e3
-        return rows, (str(k_total) if more else None)
+        """(rows, token) of the page, or None: the caller takes the full path (``DeviceMirror.page``)."""
+        return self.mirror.page(prog, sort, kernels, offset, limit)
 
     def query(self, q: dict[str, Any], kernels=None) -> tuple[list[str], str | None]:
         """Returns (keys in result order for the requested page, continuation token)."""

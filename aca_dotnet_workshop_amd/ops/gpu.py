@@ -9,6 +9,8 @@ import ctypes
 import threading
 from typing import Any
 
+import numpy as np
+
 from .build import LIB, build_gpu
 
 _lib = None
@@ -115,6 +117,9 @@ class GpuKernels:
         self._upload_slot = 0
 
     UPLOAD_SLOTS = 4
+    # made on first use (declared on the class: the sort-fault test builds a bare object)
+    _pinned_total = _total_event = None  # ``select``'s pinned row count and its event
+    _sort_temp = _sort_fault = None      # ``_sorted_rows``' scratch and look-back fault word
 
     def _stream(self) -> ctypes.c_void_p:
         return self._stream_handle
@@ -130,14 +135,7 @@ class GpuKernels:
         if tiles == 0:
             empty = torch.empty(0, dtype=torch.int32, device=self.device)
             return (empty, None) if return_mask else empty
-        if capacity % self.tile_rows or nrows > capacity:
-            raise ValueError("column capacity must be a multiple of the tile and >= nrows")
-        if live16.dtype != torch.int16 or live16.numel() * 16 < capacity:
-            raise ValueError("liveness mask must be int16 bits covering the capacity")
-        if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 2:
-            raise ValueError("column table must be int64 [ncols, 2]")
-        if prog.dtype != torch.int32 or prog.ndim != 2 or prog.shape[1] != 4:
-            raise ValueError("program must be int32 [L, 4]")
+        self._check_scan_args(table, live16, capacity, nrows, prog)
         with self._total_lock:  # also guards the cached scratch buffers
             nmask = tiles * self.tile_rows // 16
             mask = (torch.empty(nmask, dtype=torch.int16, device=self.device) if return_mask
@@ -181,6 +179,17 @@ class GpuKernels:
             out = out[:total]
         return (out, mask) if return_mask else out
 
+    def _check_scan_args(self, table, live16, capacity: int, nrows: int, prog) -> None:
+        torch = self.torch
+        if capacity % self.tile_rows or nrows > capacity:
+            raise ValueError("column capacity must be a multiple of the tile and >= nrows")
+        if live16.dtype != torch.int16 or live16.numel() * 16 < capacity:
+            raise ValueError("liveness mask must be int16 bits covering the capacity")
+        if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError("column table must be int64 [ncols, 2]")
+        if prog.dtype != torch.int32 or prog.ndim != 2 or prog.shape[1] != 4:
+            raise ValueError("program must be int32 [L, 4]")
+
     def _buf(self, name: str, n: int, dtype):
         """Cached device scratch of at least ``n`` elements (caller holds ``_total_lock``)."""
         t = self._bufs.get(name)
@@ -189,7 +198,7 @@ class GpuKernels:
         return t
 
     def _pinned(self):
-        p = getattr(self, "_pinned_total", None)
+        p = self._pinned_total
         if p is None:
             p = self._pinned_total = self.torch.zeros(1, dtype=self.torch.int64, pin_memory=True)
             self._total_event = self.torch.cuda.Event()
@@ -208,7 +217,6 @@ class GpuKernels:
         """Pinned, coherent, device-mapped host int32 array of at least ``n`` elements (caller
         holds ``_total_lock``): the page kernels read their tile list from it and write their
         answer into it, so a page query moves no data through copy kernels."""
-        import numpy as np
         mb = self._bufs.get(name)
         if mb is None or mb[2].size < n:
             if mb is not None:
@@ -231,7 +239,6 @@ class GpuKernels:
         segment table are staged in a pinned, device-mapped mailbox the kernel reads directly,
         instead of one copy (copyBuffer + DMA set-up) per segment.  Stream-ordered with every
         other launch of this process (the current stream)."""
-        import numpy as np
         segs = [(int(d), np.ascontiguousarray(a).view(np.uint8).reshape(-1)) for d, a in segments if a.size]
         if not segs:
             return
@@ -323,7 +330,6 @@ class GpuKernels:
         int32 rows; their number = ``cand_keys.numel()``): (rows [offset, k) of the key order,
         info [total, complete, written]).  ``stamps``: an int64 device tensor of 6 that gets
         the kernel's shader clock at its phase boundaries.  For the kernel tests."""
-        import numpy as np
         torch = self.torch
         n = int(cand_keys.numel())
         if n > self.page_cap or cand_rows.numel() != n:
@@ -363,14 +369,7 @@ class GpuKernels:
         keys, dims = [int(x) for x in keys], [int(x) for x in dims]
         if len(keys) != len(dims) or len(keys) > 3:
             raise ValueError("at most 3 key columns, one dictionary size each")
-        if capacity % self.tile_rows or nrows > capacity:
-            raise ValueError("column capacity must be a multiple of the tile and >= nrows")
-        if live16.dtype != torch.int16 or live16.numel() * 16 < capacity:
-            raise ValueError("liveness mask must be int16 bits covering the capacity")
-        if table.dtype != torch.int64 or table.ndim != 2 or table.shape[1] != 2:
-            raise ValueError("column table must be int64 [ncols, 2]")
-        if prog.dtype != torch.int32 or prog.ndim != 2 or prog.shape[1] != 4:
-            raise ValueError("program must be int32 [L, 4]")
+        self._check_scan_args(table, live16, capacity, nrows, prog)
         if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
             raise ValueError("key columns must be rows of the column table, dictionary sizes >= 0")
         ncells = 1
@@ -443,10 +442,10 @@ class GpuKernels:
         need = int(self.lib.tt_sort_pairs_temp_bytes(n, end_bit))
         if need < 0:
             raise RuntimeError("tt_sort_pairs: bad size or bit range")
-        temp = getattr(self, "_sort_temp", None)
+        temp = self._sort_temp
         if temp is None or temp.numel() < need:
             temp = self._sort_temp = self.torch.empty(max(need, 1), dtype=self.torch.uint8, device=self.device)
-        fault = getattr(self, "_sort_fault", None)
+        fault = self._sort_fault
         if fault is None:
             fault = self._sort_fault = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
         keys_out = self.torch.empty_like(keys)
@@ -464,7 +463,7 @@ class GpuKernels:
         trustworthy: the caller orders on the host instead).  The fault word is cleared, so one
         timeout costs one query its device ordering, not every later one.  Reads one device
         word: call it where the caller synchronises anyway."""
-        fault = getattr(self, "_sort_fault", None)
+        fault = self._sort_fault
         if fault is None or int(fault.item()) == 0:
             return True
         fault.zero_()
@@ -472,7 +471,6 @@ class GpuKernels:
         return False
 
     def _top_k(self, keys, rows, k: int, shift: int, hist, key_bits: int = 63):
-        import numpy as np
         torch = self.torch
         n = keys.numel()
         cum = np.cumsum(hist.cpu().numpy().astype(np.int64))

@@ -1,4 +1,4 @@
-// One launch per mirror sync (ops/columnar.py ColumnarIndex.to_device, backing/accel.py's
+// One launch per mirror sync (ops/device_mirror.py DeviceMirror.sync, backing/accel.py's
 // background sync): the rows appended to the column mirror since the last sync -- every
 // column's codes, the insertion sequence, the liveness words, the sort plan's rank tails -- are
 // staged by the host in ONE pinned, coherent, device-mapped buffer (the same mailbox memory the

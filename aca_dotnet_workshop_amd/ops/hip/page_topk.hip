@@ -23,7 +23,7 @@
 //   resets the candidate counter for the next query, so the page path launches no fill kernel.
 //
 // At 1e8 rows the page costs a handful of tiles instead of 12,207 (profiles/r3_page_topk.md).
-#include "scan_common.h"
+#include "sort_key.h"
 
 namespace {
 
@@ -31,19 +31,6 @@ constexpr int kPageCap = 8192;       // candidate pairs one workgroup sorts in L
 constexpr int kTopkBlock = 1024;
 constexpr int kGatherBlock = kTileRows / kRowsPerLane;  // 512 lanes x 16 rows = one tile
 constexpr int kZoneBlock = 256;      // 32 rows per lane
-constexpr int kMaxSortKeys = 4;
-
-struct SortSpec {     // host-built, one per sort key (primary first); layout of sort_keys.hip's
-  int32_t col;        // column index into the column table
-  int32_t rank_off;   // offset of this key's rank table in `ranks`
-  int32_t nranks;     // entries in this key's rank table (dictionary size)
-  int32_t bits;       // key field width
-  int32_t desc;       // 1 = descending
-  int32_t missing;    // rank of a missing path
-  int32_t max_rank;   // for DESC: stored value = max_rank - rank
-  int32_t pad;
-};
-
 // The packed ordering keys (identical to tt_sort_keys and ColumnarIndex.sort_keys_numpy) of the
 // 16 rows [row0, row0 + 16) (row0 a multiple of 16), for the rows set in
 // `sel` (others are left 0): per sort key one vector load of the 16 codes, then the rank lookups
@@ -65,10 +52,7 @@ __device__ __forceinline__ void keys16(const ColumnDesc* cols, const SortSpec* s
       if (((sel >> i) & 1u) && ids[i] >= 0 && ids[i] < s.nranks) r[i] = ranks[s.rank_off + ids[i]];
     }
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int32_t v = s.desc ? s.max_rank - r[i] : r[i];
-      k[i] = (k[i] << s.bits) | (uint64_t)(uint32_t)v;
-    }
+    for (int i = 0; i < 16; ++i) k[i] = pack_rank(k[i], s, r[i]);
   }
   const uint4* sp = reinterpret_cast<const uint4*>(seq + row0);
   uint32_t q[16];
@@ -78,7 +62,7 @@ __device__ __forceinline__ void keys16(const ColumnDesc* cols, const SortSpec* s
     q[4 * v] = x.x; q[4 * v + 1] = x.y; q[4 * v + 2] = x.z; q[4 * v + 3] = x.w;
   }
 #pragma unroll
-  for (int i = 0; i < 16; ++i) k[i] = (k[i] << seq_bits) | (uint64_t)q[i];
+  for (int i = 0; i < 16; ++i) k[i] = pack_seq(k[i], seq_bits, q[i]);
 }
 
 __device__ __forceinline__ void min_pair(uint64_t& k, int32_t& r, uint64_t k2, int32_t r2) {

@@ -241,12 +241,7 @@ tt_rank_encode(const ColumnDesc* __restrict__ src, const int32_t* __restrict__ r
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   auto one = [&](int64_t row) {
-    uint32_t raw;
-    if (cd.width == 0) raw = (reinterpret_cast<const uint8_t*>(cd.ptr)[row >> 2] >> ((row & 3) * 2)) & 3u;
-    else if (cd.width == 1) raw = reinterpret_cast<const uint8_t*>(cd.ptr)[row];
-    else if (cd.width == 2) raw = reinterpret_cast<const uint16_t*>(cd.ptr)[row];
-    else raw = reinterpret_cast<const uint32_t*>(cd.ptr)[row];
-    store_rank(dst_ptr, dst_width, row, rank_of(id_of(raw, cd.width), lds_rank, rank_table, nranks, staged));
+    store_rank(dst_ptr, dst_width, row, rank_of(load_id(cd, row), lds_rank, rank_table, nranks, staged));
   };
   if (a >= b) {  // short range: row by row
     for (int64_t row = lo + tid; row < hi; row += stride) one(row);

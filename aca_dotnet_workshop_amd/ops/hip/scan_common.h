@@ -1,5 +1,6 @@
-// Shared device code of the gfx950 query kernels (query_scan.hip, page_topk.hip): the column
-// descriptor table, the narrow-code loads and the postfix filter interpreter over 16-row groups.
+// Shared device code of the gfx950 query kernels (query_scan.hip, group_agg.hip, sort_keys.hip,
+// page_topk.hip): the column descriptor table, the narrow-code loads (ops/codes.py is the host's
+// side of that layout) and the postfix filter interpreter over 16-row groups.
 // See query_scan.hip for the data model.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +30,14 @@ __device__ __forceinline__ int32_t id_of(uint32_t raw, int width) {
   if (width == 1) return raw == 0xFFu ? -1 : (int32_t)raw;
   if (width == 2) return raw == 0xFFFFu ? -1 : (int32_t)raw;
   return (int32_t)raw;
+}
+
+// The id of one row of one column.
+__device__ __forceinline__ int32_t load_id(const ColumnDesc& cd, int64_t row) {
+  if (cd.width == 0) return id_of((reinterpret_cast<const uint8_t*>(cd.ptr)[row >> 2] >> ((row & 3) * 2)) & 3u, 0);
+  if (cd.width == 1) return id_of(reinterpret_cast<const uint8_t*>(cd.ptr)[row], 1);
+  if (cd.width == 2) return id_of(reinterpret_cast<const uint16_t*>(cd.ptr)[row], 2);
+  return id_of(reinterpret_cast<const uint32_t*>(cd.ptr)[row], 4);
 }
 
 // Load the 16 ids of rows [row0, row0+16) of one column.

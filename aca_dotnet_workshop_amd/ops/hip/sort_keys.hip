@@ -3,62 +3,20 @@
 // The query API orders results by up to a few document paths (ASC/DESC) with ties broken by
 // insertion order (backing/accel.py, ops/columnar.py ColumnarIndex.order -- the native
 // engine's semantics).  For a selection produced by tt_scan_compact this kernel packs, per
-// selected row, one 63-bit unsigned key
-//
-//     [rank(key0) | rank(key1) | ... | seq]          (most significant first)
-//
-// where rank(k) is the value's position in the column dictionary's sort order (missing paths
-// rank like null; DESC keys store max_rank - rank), and seq is the document's insertion
-// sequence.  Sorting the keys (radix sort / top-k) then yields exactly the host ordering.
+// selected row, the 63-bit unsigned key of sort_key.h; sorting the keys (radix sort / top-k)
+// then yields exactly the host ordering.
 // Rank lookups go through a small per-key rank table (dictionary id -> rank) staged in LDS
 // when it fits (it is gathered once per row and per key, so LDS keeps those random reads
 // off HBM).
 //
 // Layout: one thread per selected row, 256-thread blocks; rows are ascending row ids, so the
 // id / seq gathers of neighbouring lanes hit neighbouring addresses.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "sort_key.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxKeys = 4;
 constexpr int kLdsRankWords = 8192;  // 32 KiB of rank tables in LDS (all keys together)
 constexpr int kHistBins = 4096;      // 12-bit radix-select histogram (top-k)
-
-struct SortColumn {   // 16 bytes, same layout as the scan kernel's ColumnDesc
-  uint64_t ptr;
-  int32_t width;      // 1, 2 or 4 bytes per row; 0 = 2 bits per row
-  int32_t pad;
-};
-
-struct SortSpec {     // host-built, one per sort key (primary first)
-  int32_t col;        // column index into the column table
-  int32_t rank_off;   // offset of this key's rank table in `ranks`
-  int32_t nranks;     // entries in this key's rank table (dictionary size)
-  int32_t bits;       // key field width
-  int32_t desc;       // 1 = descending
-  int32_t missing;    // rank of a missing path
-  int32_t max_rank;   // for DESC: stored value = max_rank - rank
-  int32_t pad;
-};
-
-__device__ __forceinline__ int32_t load_id(const SortColumn& c, int64_t row) {
-  if (c.width == 0) {  // 2-bit codes, 3 = missing
-    const uint32_t v = (reinterpret_cast<const uint8_t*>(c.ptr)[row >> 2] >> ((row & 3) * 2)) & 3u;
-    return v == 3u ? -1 : (int32_t)v;
-  }
-  if (c.width == 1) {
-    const uint32_t v = reinterpret_cast<const uint8_t*>(c.ptr)[row];
-    return v == 0xFFu ? -1 : (int32_t)v;
-  }
-  if (c.width == 2) {
-    const uint32_t v = reinterpret_cast<const uint16_t*>(c.ptr)[row];
-    return v == 0xFFFFu ? -1 : (int32_t)v;
-  }
-  return reinterpret_cast<const int32_t*>(c.ptr)[row];
-}
 
 }  // namespace
 
@@ -68,7 +26,7 @@ __device__ __forceinline__ int32_t load_id(const SortColumn& c, int64_t row) {
 // With `hist != nullptr` the 12-bit radix-select histogram of the keys (bits [shift, shift+12))
 // is accumulated in the same pass (LDS-privatised, one global atomic per non-empty bin).
 extern "C" __global__ void __launch_bounds__(kBlock)
-tt_sort_keys(const SortColumn* __restrict__ cols, const int32_t* __restrict__ rows, int64_t n,
+tt_sort_keys(const ColumnDesc* __restrict__ cols, const int32_t* __restrict__ rows, int64_t n,
              const SortSpec* __restrict__ specs, int32_t nkeys, const int32_t* __restrict__ ranks,
              int32_t rank_words, const uint32_t* __restrict__ seq, int32_t seq_bits, uint64_t* __restrict__ keys,
              uint32_t* __restrict__ hist, int32_t shift) {
@@ -76,8 +34,8 @@ tt_sort_keys(const SortColumn* __restrict__ cols, const int32_t* __restrict__ ro
   extern __shared__ uint32_t lds_dyn[];
   uint32_t* lds_hist = lds_dyn;
   int32_t* lds_ranks = reinterpret_cast<int32_t*>(lds_dyn + (hist ? kHistBins : 0));
-  __shared__ SortSpec lds_specs[kMaxKeys];
-  __shared__ SortColumn lds_cols[kMaxKeys];
+  __shared__ SortSpec lds_specs[kMaxSortKeys];
+  __shared__ ColumnDesc lds_cols[kMaxSortKeys];
   const bool staged = rank_words <= kLdsRankWords;
   if (staged)
     for (int i = threadIdx.x; i < rank_words; i += kBlock) lds_ranks[i] = ranks[i];
@@ -97,10 +55,9 @@ tt_sort_keys(const SortColumn* __restrict__ cols, const int32_t* __restrict__ ro
       const int32_t id = load_id(lds_cols[j], row);
       int32_t r = s.missing;
       if (id >= 0 && id < s.nranks) r = staged ? lds_ranks[s.rank_off + id] : ranks[s.rank_off + id];
-      if (s.desc) r = s.max_rank - r;
-      k = (k << s.bits) | (uint64_t)(uint32_t)r;
+      k = pack_rank(k, s, r);
     }
-    k = (k << seq_bits) | (uint64_t)seq[row];
+    k = pack_seq(k, seq_bits, seq[row]);
     keys[i] = k;
     if (hist) atomicAdd(&lds_hist[(uint32_t)(k >> shift) & (kHistBins - 1)], 1u);
   }
@@ -115,19 +72,19 @@ extern "C" int tt_launch_sort_keys(const void* cols, const int32_t* rows, int64_
                                    const int32_t* ranks, int32_t rank_words, const uint32_t* seq, int32_t seq_bits,
                                    uint64_t* keys, uint32_t* hist, int32_t shift, hipStream_t stream) {
   if (n <= 0) return 0;
-  if (nkeys < 0 || nkeys > kMaxKeys || seq_bits < 0 || seq_bits > 32 || shift < 0 || shift > 63) return -1;
+  if (nkeys < 0 || nkeys > kMaxSortKeys || seq_bits < 0 || seq_bits > 32 || shift < 0 || shift > 63) return -1;
   // a bounded grid (8 blocks per CU on 256 CUs): each thread loops over many rows, so the LDS
   // staging and the histogram flush (<= 4096 global atomics per block) are amortised
   int64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 2048) blocks = 2048;
   const size_t lds = ((hist ? kHistBins : 0) + (rank_words <= kLdsRankWords ? rank_words : 0)) * sizeof(uint32_t);
   hipLaunchKernelGGL(tt_sort_keys, dim3((unsigned)blocks), dim3(kBlock), lds, stream,
-                     reinterpret_cast<const SortColumn*>(cols), rows, n, reinterpret_cast<const SortSpec*>(specs), nkeys,
+                     reinterpret_cast<const ColumnDesc*>(cols), rows, n, reinterpret_cast<const SortSpec*>(specs), nkeys,
                      ranks, rank_words, seq, seq_bits, keys, hist, shift);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-extern "C" int tt_sort_max_keys() { return kMaxKeys; }
+extern "C" int tt_sort_max_keys() { return kMaxSortKeys; }
 extern "C" int tt_lds_rank_words() { return kLdsRankWords; }
 
 // ---------------------------------------------------------------------------------------

@@ -167,21 +167,21 @@ def main() -> None:
     ix.n = n
     ix.keys = []  # not needed for the scan benchmark
     ix.version += 1
-    ix._full_dirty = True
+    ix.mirror.invalidate()
 
     k = GpuKernels("cuda:0")
     flt = {"AND": [{"LT": {"taskDueDate": "2024-07-01T00:00:00"}}, {"EQ": {"isCompleted": False}},
                    {"EQ": {"isOverDue": False}}]}
     prog = ix.compile(flt)
-    st, code, bm = ix.device_program(prog, k)  # includes rank-encoding range-leaf columns
+    m, code, bm = ix.mirror.program(prog, k)  # includes rank-encoding range-leaf columns
 
     def timed(**kw):
         for _ in range(a.warmup):
-            res = k.select(st["table"], st["live"], ix.cap, n, code, bm, **kw)
+            res = k.select(m.table, m.live, ix.cap, n, code, bm, **kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(a.iters):
-            res = k.select(st["table"], st["live"], ix.cap, n, code, bm, **kw)
+            res = k.select(m.table, m.live, ix.cap, n, code, bm, **kw)
         torch.cuda.synchronize()
         return res, (time.perf_counter() - t0) / a.iters
 
@@ -191,7 +191,7 @@ def main() -> None:
     # bytes per row of the columns the scan reads (2-bit codes: width 0 = 1/4 byte; range leaves
     # read their rank-encoded copy, at least one byte)
     rank_cols = set(prog.code[prog.code[:, 0] == 7, 1].tolist())
-    widths = sum((max(1, st["widths"][c]) if c in rank_cols else (st["widths"][c] or 0.25)) for c in prog.columns)
+    widths = sum((max(1, m.widths[c]) if c in rank_cols else (m.widths[c] or 0.25)) for c in prog.columns)
     nbytes = n * widths + n // 8 + 2 * n // 8 + selected * 4
     res = {"metric": "overdue_sweep_rows_per_sec", "value": round(n / dt, 1), "unit": "rows/s", "rows": n,
            "selected": selected, "ms_per_query": round(dt * 1e3, 4), "effective_GBps": round(nbytes / dt / 1e9, 1),
@@ -213,7 +213,7 @@ def main() -> None:
         ids[0, :n] = np.arange(n, dtype=np.int64) // 64
         ix.ids = np.concatenate([ix.ids, ids])
         ix.version += 1
-        ix._full_dirty = True
+        ix.mirror.invalidate()
         ix.seq[:n] = np.arange(1, n + 1)
         sort = [{"key": "taskCreatedOn", "order": "ASC"}]
         q = {"filter": flt, "sort": sort, "page": {"limit": 1000}}
@@ -246,9 +246,9 @@ def main() -> None:
         res["page_match"] = bool(np.array_equal(rows, want)) and token == "1000"
     if a.sorted:
         ix.seq[:n] = rng.permutation(n) + 1  # updates move rows: result order != row order
-        ix._full_dirty = True
+        ix.mirror.invalidate()
         sort = [{"key": "taskDueDate", "order": "DESC"}]
-        st = ix.to_device(k)
+        ix.mirror.sync(k)
         # the device ordering: tt_sort_keys + the repo's onesweep LSD radix sort of (key, row) pairs
         # over the used key bits (hip/radix_pairs.hip), or radix select + sort for the top 100
         for label, kk in (("top100", 100), ("full", None)):
@@ -277,7 +277,7 @@ def main() -> None:
                 return f"task-{i}"
         ix.keys = _Keys()
         ix.seq[:n] = rng.permutation(n) + 1
-        ix._full_dirty = True
+        ix.mirror.invalidate()
         q = {"filter": flt, "sort": [{"key": "taskDueDate", "order": "DESC"}], "page": {"limit": 100}}
         for _ in range(3):
             ix.query(q, k)

@@ -60,7 +60,7 @@ def main() -> None:
         for _ in range(1300):
             store.set(f"{PREFIX}{i:08d}", doc(i))
             i += 1
-        before = dict(ix.timing)
+        before = dict(ix.mirror.timing)
         t = time.perf_counter()
         ix.sync()
         t_sync = time.perf_counter() - t
@@ -71,7 +71,7 @@ def main() -> None:
         t_q = time.perf_counter() - t
         if rnd >= 10:
             prof.disable()
-            d = {key: ix.timing.get(key, 0.0) - before.get(key, 0.0) for key in ix.timing}
+            d = {key: ix.mirror.timing.get(key, 0.0) - before.get(key, 0.0) for key in ix.mirror.timing}
             per.append((t_sync * 1e3, t_q * 1e3, d))
     print("per query (ms, median of 30): sync %.3f, query %.3f" % (np.median([p[0] for p in per]), np.median([p[1] for p in per])))
     for key in ("page_plan_ms", "page_program_ms", "page_zones_ms", "page_kernels_ms"):

@@ -414,7 +414,7 @@ def test_gpu_incremental_sync_and_width_growth():
         ix.upsert(str(i), {"v": rnd.randrange(200), "flag": i % 3 == 0})
     prog = ix.compile({"AND": [{"LT": {"v": 100}}, {"EQ": {"flag": True}}]})
     assert np.array_equal(ix.select_gpu(prog, k), ix.select_numpy(prog))
-    assert ix._dev["widths"][ix.col_of["v"]] == 1
+    assert ix.mirror.widths[ix.col_of["v"]] == 1
     # appends + tombstones + a dictionary that outgrows 8 and then 16 bits
     for i in range(30000, 100000):
         ix.upsert(str(i), {"v": i, "flag": i % 5 == 0})
@@ -425,7 +425,7 @@ def test_gpu_incremental_sync_and_width_growth():
     for f in ({"AND": [{"LT": {"v": 100}}, {"EQ": {"flag": True}}]}, {"GTE": {"v": 70000}}, {"NEQ": {"flag": True}}):
         prog = ix.compile(f)
         assert np.array_equal(ix.select_gpu(prog, k), ix.select_numpy(prog)), f
-    assert ix._dev["widths"][ix.col_of["v"]] == 4
+    assert ix.mirror.widths[ix.col_of["v"]] == 4
     ix.compact()
     prog = ix.compile({"LT": {"v": 1000}})
     assert np.array_equal(ix.select_gpu(prog, k), ix.select_numpy(prog))
@@ -463,13 +463,13 @@ def test_gpu_two_bit_columns():
             ix.upsert(str(n), d)
             n += 1
         check(f"n={n}")
-    assert ix._dev["widths"][ix.col_of["done"]] == 0 and ix._dev["widths"][ix.col_of["state"]] == 0
+    assert ix.mirror.widths[ix.col_of["done"]] == 0 and ix.mirror.widths[ix.col_of["state"]] == 0
     for i in rnd.sample(range(n), 300):
         ix.delete(str(i))
     check("tombstones")
     ix.upsert("grow", {"done": True, "state": "c"})  # 4 distinct values: the column becomes 1 byte
     check("grown")
-    assert ix._dev["widths"][ix.col_of["state"]] == 1
+    assert ix.mirror.widths[ix.col_of["state"]] == 1
 
 
 def _interleaved(ix, store, rnd, kernels=None, rounds=12):
@@ -581,7 +581,7 @@ def test_gpu_rank_encode_unaligned_ranges(ndistinct):
     for f in ({"LT": {"v": lo_v}}, {"GTE": {"v": lo_v}}):
         prog = ix.compile(f)
         assert np.array_equal(ix.select_gpu(prog, k), ix.select_numpy(prog)), f
-    assert ix._dev["ranks"][ix.col_of["v"]]["w"] == {50: 1, 3000: 2, 70_000: 4}[ndistinct]
+    assert ix.mirror.ranks[ix.col_of["v"]].w == {50: 1, 3000: 2, 70_000: 4}[ndistinct]
     for extra in (37, 5, 16, 1):  # incremental syncs of existing values (no rank shift)
         base = ix.n
         for i in range(base, base + extra):
@@ -950,7 +950,7 @@ def test_device_sort_plan_grows_in_place_and_matches_the_host_keys():
     sort = [{"key": "c"}, {"key": "d", "order": "DESC"}]
 
     def check():
-        hit = ix._device_sort_plan(sort, fk)
+        hit = ix.mirror.sort_plan(sort, fk)
         rows = np.nonzero(ix.live[:ix.n])[0]
         want = ix.sort_keys_numpy(rows, ix.sort_specs(sort))
         assert np.array_equal(ix.sort_keys_numpy(rows, hit[4]), want)
@@ -1018,11 +1018,11 @@ def test_gpu_page_path_matches_host(sort):
             token = None
             for _ in range(3):
                 page = {"limit": limit, **({"token": token} if token else {})}
-                before = ix._zones.copy()
+                before = ix.mirror.zones.copy()
                 got = ix.query({**q, "page": page}, k)
                 want = ix.query({**q, "page": page})
                 assert got == want, (round_, limit, token)
-                used += bool(ix._zones) or bool(before)
+                used += bool(ix.mirror.zones) or bool(before)
                 token = got[1]
                 if token is None:
                     break
@@ -1033,7 +1033,7 @@ def test_gpu_page_path_matches_host(sort):
             else:
                 ix.upsert(f"k{i}", {"c": f"2025-03-01T{i // 3600:02d}:{i // 60 % 60:02d}:{i % 60:02d}",
                                     "d": rnd.randrange(40), "x": rnd.random() < 0.3})
-    assert used and ix._zones
+    assert used and ix.mirror.zones
 
 
 @pytest.mark.gpu
@@ -1099,10 +1099,10 @@ def test_gpu_zone_argmin_matches_numpy():
     for i in rnd.sample(range(50_000), 9000):
         ix.delete(str(i))
     sort = [{"key": "c", "order": "DESC"}]
-    specs_t, ranks_t, seq_bits, _, plan = ix._device_sort_plan(sort, k)
-    st = ix.to_device(k)
+    specs_t, ranks_t, seq_bits, _, plan = ix.mirror.sort_plan(sort, k)
+    m = ix.mirror.sync(k)
     tiles = np.arange((ix.n + TILE_ROWS - 1) // TILE_ROWS, dtype=np.int32)
-    got = k.zone_argmin(st["table"], st["live"], ix.n, specs_t, ranks_t, st["seq"], seq_bits, tiles)
+    got = k.zone_argmin(m.table, m.live, ix.n, specs_t, ranks_t, m.seq, seq_bits, tiles)
     for t, r in zip(tiles.tolist(), got.tolist()):
         rows = np.arange(t * TILE_ROWS, min((t + 1) * TILE_ROWS, ix.n))
         rows = rows[ix.live[rows] != 0]

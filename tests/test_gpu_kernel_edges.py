@@ -235,6 +235,20 @@ def test_pack_layout_by_hand():
     assert _live16([1, 0, 0, 1] + [0] * 12 + [1], TILE).view(np.uint16)[:3].tolist() == [0b1001, 1, 0]
 
 
+def test_index_codes_follow_the_hand_packed_layout():
+    """``ops/codes.py`` (what the index uploads) on the example above, and the id -> value gather."""
+    from aca_dotnet_workshop_amd.ops.codes import encode_codes, gather
+    ids = np.array([0, 1, 2, -1, 2, -1, 0, 1], dtype=np.int32)
+    assert encode_codes(ids, 0).tolist() == [0b11_10_01_00, 0b01_00_11_10]
+    for w, nbytes in ((0, 2), (1, 8), (2, 16), (4, 32)):
+        got = encode_codes(ids, w)
+        assert got.nbytes == nbytes and got.tobytes() == _pack(ids, w, TILE).tobytes()[:nbytes]
+    assert encode_codes(ids, 4) is ids
+    table = np.array([10, 20, 30], dtype=np.int64)
+    assert gather(table, ids, -7).tolist() == [10, 20, 30, -7, 30, -7, 10, 20]
+    assert gather(table[:0], np.array([-1, -1]), 5).tolist() == [5, 5]
+
+
 @pytest.mark.parametrize("sort", [[], [{"key": "m", "order": "DESC"}], [{"key": "x"}, {"key": "s", "order": "DESC"}],
                                   [{"key": "s"}, {"key": "m"}, {"key": "w", "order": "DESC"}, {"key": "x"}]])
 def test_ref_keys_match_the_host_sort_keys(host_index, sort):
@@ -881,7 +895,7 @@ def test_gpu_queries_at_the_width_switches(k):
             prog = ix.compile(f)
             want = ix.select_numpy(prog)
             assert np.array_equal(ix.select_gpu(prog, k), want) and want.size, (size, f)
-        assert ix._dev["widths"][col] == width and ix._dev["ranks"][col]["w"] == rank_width
+        assert ix.mirror.widths[col] == width and ix.mirror.ranks[col].w == rank_width
         sort = [{"key": "v", "order": "DESC"}]
         for q in ({"sort": sort, "page": {"limit": 50}}, {"sort": sort},
                   {"filter": {"LTE": {"v": newest}}, "sort": sort}):
