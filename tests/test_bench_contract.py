@@ -182,15 +182,25 @@ def test_bench_two_ranks_torchrun():
     assert [x for x in r.stdout.splitlines() if x.strip() and not x.startswith("{")] == [], r.stdout
     _check(lines[0], 2, 2, 1)
     # each rank pinned to its own partition of the host (the stack inherits the mask)
-    from aca_dotnet_workshop_amd.parallel import cpu_quota, host_topology, one_thread_per_core, partition_cpus
+    from aca_dotnet_workshop_amd.parallel import (cpu_quota, host_topology, one_thread_per_core, partition_cpus,
+                                                  rank_gpu_node)
     nodes, core = host_topology()
-    part = partition_cpus(set(os.sched_getaffinity(0)), nodes, core, 0, 2)
-    want = f"{len(part)} CPUs per rank (NUMA-local whole cores (rank order))" if part else "none"
+    allowed = set(os.sched_getaffinity(0))
+    part, mode = partition_cpus(allowed, nodes, core, 0, 2), "NUMA-local whole cores (rank order)"
+    mine = rank_gpu_node(0, nodes)
+    if mine is not None and nodes[mine] & allowed:
+        # sysfs names the NUMA node of rank 0's GPU: the ranks whose GPUs sit there share its CPUs
+        peers = [r for r in range(2) if rank_gpu_node(r, nodes) == mine]
+        order = sorted(nodes[mine] & allowed, key=lambda c: (core.get(c, c), c))
+        local = set(order[:len(order) // len(peers)])
+        if len(local) >= 2:
+            part, mode = local, f"GPU-local NUMA node {mine}, whole cores"
+    want = f"{len(part)} CPUs per rank ({mode})" if part else "none"
     q = cpu_quota()
     if part and q is not None and q / 2 <= len(one_thread_per_core(part, core)):  # quota below the cores
         phys = one_thread_per_core(part, core)
         if len(phys) >= 2:
-            want = f"{len(phys)} CPUs per rank (NUMA-local whole cores (rank order), one thread per core)"
+            want = f"{len(phys)} CPUs per rank ({mode}, one thread per core)"
     assert lines[0]["config"]["cpu_pinning"] == want
 
 

@@ -843,8 +843,11 @@ def test_bulk_string_encode_and_append_ranks(rank_path):
 
 class _FakePageKernels:
     """The page path's kernels (hip/page_topk.hip) emulated on the host over the index's own
-    arrays, so ``ColumnarIndex.page_gpu``'s zone maps, tile choice, retries and continuation
-    tokens run in the CPU suite; the real kernels are pinned by the GPU tests below."""
+    arrays: what ``ref_page`` of test_gpu_kernel_edges is checked against.  The page-path tests
+    below run over ``HostKernels`` (test_device_mirror_state), which answers from the buffers the
+    mirror uploaded, so ``ColumnarIndex.page_gpu``'s zone maps, tile choice, retries and
+    continuation tokens -- and the uploads under them -- run in the CPU suite; the real kernels
+    are pinned by the GPU tests."""
 
     def __init__(self, ix, cap=8192):
         import torch
@@ -907,14 +910,13 @@ def test_page_path_host_logic_matches_full_order(seed, sort, limit):
     for i in range(30_000):
         ix.upsert(f"k{i}", {"c": f"2025-01-{rnd.randrange(1, 29):02d}T{rnd.randrange(24):02d}:00:00",
                             "d": rnd.randrange(50), "x": rnd.random() < 0.2})
-    fk = _FakePageKernels(ix)
-    fk.sort = sort
+    from test_device_mirror_state import HostKernels
+    fk = HostKernels()  # answers from what the mirror uploaded, not from the index
     flt = {"AND": [{"EQ": {"x": False}}, {"LT": {"d": 40}}]}
     for rnd_ in range(3):
         q = {"filter": flt, **({"sort": sort} if sort else {})}
         full, _ = ix.query(q)
         prog = ix.compile(flt)
-        fk.prog = prog
         got, token, ended = [], None, False
         for _ in range(25):
             off = int(token or 0)
@@ -945,8 +947,9 @@ def test_device_sort_plan_grows_in_place_and_matches_the_host_keys():
     values landing inside the order re-copy the ids whose rank moved.  The packed keys it yields
     always equal the host reference's."""
     import torch
+    from test_device_mirror_state import HostKernels, assert_mirror_matches_index
     ix = ColumnarIndex(["c", "d"])
-    fk = _FakePageKernels(ix)
+    fk = HostKernels()  # uploads copy: the device table below is a buffer of its own
     sort = [{"key": "c"}, {"key": "d", "order": "DESC"}]
 
     def check():
@@ -954,7 +957,10 @@ def test_device_sort_plan_grows_in_place_and_matches_the_host_keys():
         rows = np.nonzero(ix.live[:ix.n])[0]
         want = ix.sort_keys_numpy(rows, ix.sort_specs(sort))
         assert np.array_equal(ix.sort_keys_numpy(rows, hit[4]), want)
+        assert not np.shares_memory(hit[1].numpy(), hit[4][1])
         assert torch.equal(hit[1], torch.from_numpy(hit[4][1]))  # device table == host table
+        ix.mirror.sync(fk)
+        assert_mirror_matches_index(ix, fk, lambda t: t.numpy(), plans=[sort])  # ... == the keys' rank tables
         return hit
     for i in range(3000):
         ix.upsert(f"k{i}", {"c": f"2026-01-01T00:{i // 60:02d}:{i % 60:02d}", "d": i % 7})
@@ -985,15 +991,15 @@ def test_page_path_overflow_and_tiny_cap_fall_back():
     ix = ColumnarIndex(["c"])
     for i in range(40_000):
         ix.upsert(f"k{i}", {"c": i // 40})  # clustered by tile, like a creation timestamp
-    fk = _FakePageKernels(ix)  # the device cap is one tile: a single tile always fits
-    fk.sort = [{"key": "c"}]
+    from test_device_mirror_state import HostKernels
+    fk = HostKernels()  # the device cap is one tile: a single tile always fits
+    sort = [{"key": "c"}]
     prog = ix.compile({})
-    fk.prog = prog
-    rows, token = ix.page_gpu(prog, fk.sort, fk, 0, 100)
-    assert [ix.keys[r] for r in rows] == ix.query({"sort": fk.sort, "page": {"limit": 100}})[0] and token == "100"
-    assert ix.page_gpu(prog, fk.sort, fk, 8100, 200) is None  # beyond the capacity
+    rows, token = ix.page_gpu(prog, sort, fk, 0, 100)
+    assert [ix.keys[r] for r in rows] == ix.query({"sort": sort, "page": {"limit": 100}})[0] and token == "100"
+    assert ix.page_gpu(prog, sort, fk, 8100, 200) is None  # beyond the capacity
     fk.page_cap = 16  # a tile's matches alone overflow: the full path answers
-    assert ix.page_gpu(prog, fk.sort, fk, 0, 10) is None
+    assert ix.page_gpu(prog, sort, fk, 0, 10) is None
 
 
 @pytest.mark.gpu

@@ -1,0 +1,879 @@
+"""``DeviceMirror``'s incremental sync against a from-scratch upload.
+
+The invariant the design rests on: after any history of writes and syncs the device holds exactly
+what a full upload of the current index would put there.  ``assert_mirror_matches_index`` reads
+every buffer the mirror keeps (code columns, liveness, sequence, rank columns and their tables,
+the descriptor table, the sort plans' rank tables, the zone maps) and compares it with values
+computed from the index and the NumPy references of ``test_gpu_kernel_edges`` alone.
+
+The histories below are seeded scripts that call it after every ``sync`` / ``program`` /
+``sort_plan`` / ``page`` / ``warm``.  On a machine without a GPU they run over ``HostKernels``,
+a stand-in "device" that owns its memory (uploads copy) and answers every query from the buffers
+it is handed, decoding the descriptor table by address; the ``gpu`` tests run the same script
+functions over ``GpuKernels`` and read the buffers back.
+"""
+import ctypes
+import json
+import random
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from aca_dotnet_workshop_amd import native
+from aca_dotnet_workshop_amd.ops.codes import OP_RANGE, encode_codes, gather, width_for
+from aca_dotnet_workshop_amd.ops.columnar import ColumnarIndex, Program
+from test_gpu_kernel_edges import MISSING, TILE, _live16, _pack, ref_keys, ref_page, ref_select
+
+_CODE_DT = {1: np.uint8, 2: np.uint16, 4: np.int32}
+
+
+# ------------------------------------------------------------------ the device layout, read back
+def _unpack(raw, width, rows):
+    """The inverse of ``_pack``: int32 ids (-1 = missing) of the first ``rows`` rows of a column's
+    bytes in the device layout."""
+    raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+    if width == 4:
+        return raw[:4 * rows].view("<i4").astype(np.int32)
+    if width == 0:
+        b = raw[:(rows + 3) // 4]
+        c = ((b[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:rows].astype(np.int32)
+    else:
+        c = raw[:width * rows].view({1: np.uint8, 2: "<u2"}[width]).astype(np.int32)
+    return np.where(c == MISSING[width], -1, c).astype(np.int32)
+
+
+def _peek(address, nbytes):
+    """A copy of ``nbytes`` of host memory at ``address`` (what a kernel reads through a descriptor)."""
+    return np.frombuffer(ctypes.string_at(int(address), int(nbytes)), dtype=np.uint8)
+
+
+def _column_at(address, width, rows):
+    return _unpack(_peek(address, (rows + 3) // 4 if width == 0 else rows * width), width, rows)
+
+
+@pytest.mark.parametrize("width,top", [(0, 2), (1, 254), (2, 65534), (4, (1 << 31) - 1)])
+def test_unpack_inverts_pack(width, top):
+    rng = np.random.default_rng(width)
+    for n in (0, 1, 5, TILE - 3, TILE + 7):
+        ids = rng.integers(-1, min(top, 70_000) + 1, n).astype(np.int32)
+        if n > 2:
+            ids[:3] = [top, -1, 0]
+        cap = 2 * TILE
+        want = np.full(cap, -1, dtype=np.int32)
+        want[:n] = ids
+        assert np.array_equal(_unpack(_pack(ids, width, cap), width, cap), want)
+        assert np.array_equal(_unpack(_pack(ids, width, cap), width, n), ids)
+
+
+# ------------------------------------------------------------------ the host "device"
+class _CopyingTorch:
+    """torch, but ``from_numpy`` copies: a tensor made from an index array never shares its
+    memory (on a real device ``.to(device)`` makes that copy)."""
+
+    def __init__(self):
+        import torch
+        self._torch = torch
+
+    def from_numpy(self, a):
+        return self._torch.from_numpy(np.array(a, copy=True, order="C"))
+
+    def __getattr__(self, name):
+        return getattr(self._torch, name)
+
+
+class HostKernels:
+    """``GpuKernels`` on host memory for the CPU suite.  Uploads copy (``_CopyingTorch``, and the
+    same scatter as ``GpuKernels.upload``), ``rank_encode`` encodes, and every query is answered
+    from the buffers it is handed -- the descriptor table decoded row by row by address and
+    width, the liveness words, the sequence -- with the references of ``test_gpu_kernel_edges``;
+    never from the index.  A buffer the mirror failed to bring up to date gives a wrong answer."""
+
+    def __init__(self, cap=TILE):
+        self.torch = _CopyingTorch()
+        self.device = self.torch.device("cpu")
+        self.page_cap, self.max_sort_keys = cap, 4
+        self.lib = SimpleNamespace(tt_group_max_cells=lambda: 1 << 22)
+        self.calls = {"zone_tiles": 0, "page_tiles": 0, "pages": 0, "rank_rows": 0}
+        self.uploads = 0  # scatters that carried bytes, as GpuKernels counts them
+
+    # -- writes
+    def upload(self, segments):  # GpuKernels.upload, on host tensors: the same bytes written in place
+        self.uploads += any(a.size for _, a in segments)
+        for dst, a in segments:
+            b = np.ascontiguousarray(a)
+            ctypes.memmove(int(dst), b.ctypes.data, b.nbytes)
+
+    def rank_encode(self, src_desc, rank_table, lo, hi, dst, width):
+        """dst[lo:hi] = rank_table[id] of the source column *at the descriptor's address*, the
+        all-ones code for a missing id or one at or past the table; nothing outside [lo, hi)."""
+        if hi <= lo:
+            return
+        address, src_width = src_desc.numpy().reshape(-1)[:2].tolist()
+        ids = _column_at(address, src_width, hi)[lo:hi].astype(np.int64)
+        table = rank_table.numpy().astype(np.int64)
+        ok = (ids >= 0) & (ids < table.size)
+        miss = -1 if width == 4 else MISSING[width]
+        ranks = np.where(ok, table[np.where(ok, ids, 0)] if table.size else miss, miss)
+        out = dst.numpy().view(_CODE_DT[width])
+        out[lo:hi] = ranks.astype(np.int64).astype(_CODE_DT[width])
+        self.calls["rank_rows"] += hi - lo
+
+    # -- reads
+    @staticmethod
+    def _cols(table, rows):
+        return [(_column_at(a, w, rows), w) for a, w in table.numpy().reshape(-1, 2).tolist()]
+
+    @staticmethod
+    def _live(live16, rows):
+        return np.unpackbits(live16.numpy().view(np.uint8), bitorder="little")[:rows].astype(bool)
+
+    @staticmethod
+    def _seq(seq):
+        return seq.numpy().view(np.uint32)
+
+    def select(self, table, live16, capacity, nrows, prog, bitmaps, return_mask=False):
+        import torch
+        if nrows == 0:
+            empty = torch.zeros(0, dtype=torch.int32)
+            return (empty, None) if return_mask else empty
+        assert capacity % TILE == 0 and nrows <= capacity and live16.numel() * 16 >= capacity
+        rows = ref_select(self._cols(table, nrows), self._live(live16, nrows), nrows, prog.numpy(), bitmaps.numpy())
+        out = torch.from_numpy(rows)
+        if not return_mask:
+            return out
+        hit = np.zeros((nrows + TILE - 1) // TILE * TILE, dtype=bool)
+        hit[rows] = True
+        return out, torch.from_numpy(_live16(hit, hit.size).copy())
+
+    def zone_argmin(self, table, live16, nrows, specs, ranks, seq, seq_bits, tiles):
+        cols, live = self._cols(table, nrows), self._live(live16, nrows)
+        self.calls["zone_tiles"] += len(tiles)
+        out = []
+        for t in np.asarray(tiles).tolist():
+            rows = np.arange(t * TILE, min((t + 1) * TILE, nrows))
+            rows = rows[live[rows]]
+            keys = ref_keys(cols, rows, specs.numpy(), ranks.numpy(), self._seq(seq), seq_bits)
+            out.append(int(rows[np.argmin(keys)]) if rows.size else -1)
+        return np.asarray(out, dtype=np.int32)
+
+    def page(self, table, live16, nrows, prog, bitmaps, specs, ranks, seq, seq_bits, tiles, k, offset, bound):
+        self.calls["pages"] += 1
+        self.calls["page_tiles"] += len(tiles)
+        return ref_page(self._cols(table, nrows), self._live(live16, nrows), nrows, prog.numpy(), bitmaps.numpy(),
+                        specs.numpy(), ranks.numpy(), self._seq(seq), seq_bits, tiles, k, offset, bound,
+                        cap=self.page_cap)
+
+    def group_count(self, table, g, mask, nrows, ngroups):
+        import torch
+        ids = self._cols(table, nrows)[g][0]
+        picked = ids[self._live(mask, nrows)]
+        picked = picked[(picked >= 0) & (picked < ngroups)]
+        return torch.from_numpy(np.bincount(picked, minlength=max(ngroups, 1)).astype(np.int32))[:ngroups]
+
+    def scan_group(self, table, live16, capacity, nrows, prog, bitmaps, keys, dims, max_blocks=0, counts=None):
+        import torch
+        cols = self._cols(table, nrows)
+        rows = ref_select(cols, self._live(live16, nrows), nrows, prog.numpy(), bitmaps.numpy())
+        cell, keep, ncells = np.zeros(rows.size, dtype=np.int64), np.ones(rows.size, dtype=bool), 1
+        for c, d in zip(keys, dims):
+            ids = cols[int(c)][0][rows].astype(np.int64)
+            keep &= ids < d  # ids at or past the dictionary size are dropped
+            cell = cell * (d + 1) + np.where(ids < 0, d, ids)
+            ncells *= d + 1
+        return torch.from_numpy(np.bincount(cell[keep], minlength=ncells).astype(np.uint32).view(np.int32))
+
+    def sort_keys(self, table, rows, specs, ranks, seq, seq_bits, hist=None, shift=0):
+        import torch
+        r = rows.numpy()
+        nrows = int(r.max()) + 1 if r.size else 0
+        keys = ref_keys(self._cols(table, nrows), r, specs.numpy(), ranks.numpy(), self._seq(seq), seq_bits)
+        return torch.from_numpy(keys.view(np.int64))
+
+    def order(self, table, rows, specs, ranks, seq, seq_bits, k=None, key_bits=63):
+        import torch
+        if rows.numel() == 0:
+            return rows
+        keys = self.sort_keys(table, rows, specs, ranks, seq, seq_bits).numpy().view(np.uint64)
+        out = rows.numpy()[np.argsort(keys, kind="stable")]
+        return torch.from_numpy(out[:k] if k is not None else out)
+
+    def check_sort(self):
+        return True
+
+
+def _host():
+    return HostKernels(), lambda t: t.numpy()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    from aca_dotnet_workshop_amd.ops.gpu import GpuKernels
+    return GpuKernels(), lambda t: t.cpu().numpy()
+
+
+# ------------------------------------------------------------------ the invariant
+def _zone_reference(ix, sort):
+    """Per tile the live row with the smallest ordering key of ``sort`` (-1: none), from the index."""
+    specs, ranks, seq_bits = ix.sort_specs(sort)
+    cols = [(ix.ids[c], None) for c in range(len(ix.columns))]
+    out = []
+    for t in range((ix.n + TILE - 1) // TILE):
+        rows = np.arange(t * TILE, min((t + 1) * TILE, ix.n))
+        rows = rows[ix.live[rows] != 0]
+        out.append(int(rows[np.argmin(ref_keys(cols, rows, specs, ranks, ix.seq, seq_bits))]) if rows.size else -1)
+    return np.asarray(out, dtype=np.int32)
+
+
+def _plan_key(ix, kernels, sort):
+    return (json.dumps(sort, sort_keys=True, default=str), str(kernels.device), ix._dict_gen)
+
+
+def assert_mirror_matches_index(ix, kernels, read, rank_cols=None, plans=()):
+    """After any history the device holds what a full upload of ``ix`` would put there.  ``read``
+    gives a tensor's host bytes.  ``rank_cols``: the columns the last sync was asked to keep as
+    ranks (None: as many as the descriptor table lists); ``plans``: the sorts whose ``sort_plan``
+    ran since the last write.  Every expected value comes from ``ix`` and the NumPy references."""
+    m, n, cap = ix.mirror, ix.n, ix.cap
+    on_host = str(kernels.device) == "cpu"
+    assert (m.cap, m.synced, len(m.cols)) == (cap, n, len(ix.columns))
+    # code columns: the whole capacity -- rows past n hold the missing code -- and the padding
+    widths = [width_for(len(c.values)) for c in ix.columns]
+    assert m.widths == widths
+    for c, w in enumerate(widths):
+        want = np.ascontiguousarray(encode_codes(ix.ids[c, :cap], w)).view(np.uint8)
+        if w == 0:
+            want = np.concatenate([want, np.zeros(16, dtype=np.uint8)])
+        got = read(m.cols[c])
+        assert not on_host or not np.shares_memory(got, ix.ids), f"column {c} aliases the index"
+        got = np.ascontiguousarray(got).view(np.uint8).reshape(-1)
+        bad = np.nonzero(got != want)[0] if got.size == want.size else None
+        assert bad is not None and bad.size == 0, \
+            f"column {c} (width {w}): {None if bad is None else bad.size} stale bytes, first at {bad[:1]}"
+    # liveness over the whole capacity (rows past n are dead), sequence over the rows
+    live = read(m.live).view(np.uint16)
+    want = ix.live_words(0, cap // 16).view(np.uint16)
+    assert live.size == want.size and np.array_equal(live, want), \
+        f"stale liveness words {np.nonzero(live != want)[0][:4]}"
+    assert np.array_equal(read(m.seq)[:n].view(np.uint32), ix.seq[:n].astype(np.uint32)), "stale sequence"
+    # rank columns the last sync was asked for, in slot order behind the code columns
+    table = read(m.table).reshape(-1, 2)
+    nrank = table.shape[0] - len(widths)
+    if rank_cols is not None:
+        assert nrank == len(rank_cols), (nrank, rank_cols)
+    slots = sorted(m.rank_slot.items(), key=lambda cs: cs[1]) if nrank else []
+    assert [s for _, s in slots] == list(range(len(widths), len(widths) + nrank))
+    if rank_cols is not None:
+        assert [c for c, _ in slots] == sorted(set(rank_cols))
+    rows = [[m.cols[c].data_ptr(), w] for c, w in enumerate(widths)]
+    for col, _ in slots:
+        rc, ranks = m.ranks[col], ix.columns[col].ranks()
+        w = max(1, widths[col])
+        assert rc.w == w and rc.t.numel() == cap and rc.ver == ix.columns[col].rank_version and rc.synced == n
+        # rows past n are unspecified: a kept buffer is re-encoded over [0, n) and never cleared
+        got = read(rc.t).view(_CODE_DT[w])[:n]
+        want = encode_codes(gather(ranks, ix.ids[col, :n], -1), w)
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, f"rank column {col}: {bad.size} rows hold another rank, first {bad[:4]}"
+        if ix.columns[col].values:
+            assert np.array_equal(read(rc.table), ranks.astype(np.int32)), f"rank table of column {col}"
+        assert read(rc.src).reshape(-1).tolist() == [m.cols[col].data_ptr(), widths[col]], \
+            f"source descriptor of rank column {col}"
+        assert rc.src_key == (m.cols[col].data_ptr(), widths[col])
+        rows.append([rc.t.data_ptr(), w])
+    # the descriptor table
+    assert table.tolist() == rows, "descriptor table"
+    assert m.table_widths.tolist() == [w for _, w in rows]
+    # sort plans refreshed since the last write
+    for sort in plans:
+        ent = m._plan_cache[_plan_key(ix, kernels, sort)]
+        specs, tables, _ = ix.sort_specs(sort)
+        dev = read(ent.dev)
+        assert not on_host or not np.shares_memory(dev, ent.host)
+        assert ent.specs is not None and np.array_equal(read(ent.specs_dev), ent.specs), "plan specs on the device"
+        assert np.array_equal(np.delete(ent.specs, 1, axis=1), np.delete(specs, 1, axis=1)), "plan specs"
+        end = 0
+        for i, (_, off, size, *_rest) in enumerate(specs.tolist()):
+            o = int(ent.specs[i, 1])
+            assert o == int(ent.offs[i]) and end <= o and o + size <= dev.size and size <= ent.caps[i]
+            end = o + size
+            for name, buf in (("device", dev), ("host", ent.host)):
+                bad = np.nonzero(buf[o:o + size] != tables[off:off + size])[0]
+                assert bad.size == 0, f"sort plan {sort}, key {i}: {bad.size} stale {name} ranks, first id {bad[:1]}"
+    # zone maps: a tile the zone holds as clean has its argmin
+    for z in m.zones.values():
+        if z.all or ix.sort_specs(z.sort) is None:
+            continue
+        want = _zone_reference(ix, z.sort)
+        for t in range(min(z.zarg.size, want.size)):
+            assert t in z.dirty or z.zarg[t] == want[t], \
+                f"zone {z.sort}: tile {t} holds row {z.zarg[t]}, the argmin is {want[t]}"
+
+
+# ------------------------------------------------------------------ running a history
+class Run:
+    """One index (document-backed, or fed by a ``DocStore``'s native mirror) and one kernels
+    object; every mirror operation is followed by the invariant."""
+
+    def __init__(self, ix, kernels, read, store=None):
+        self.ix, self.k, self.read, self.store = ix, kernels, read, store
+        self.asked, self.plans, self.checks = None, [], 0
+
+    # -- writes
+    def put(self, key, doc):
+        self.plans = []
+        if self.store is None:
+            self.ix.upsert(key, doc)
+        else:
+            self.store.set(key, json.dumps(doc))
+
+    def delete(self, key):
+        self.plans = []
+        if self.store is None:
+            self.ix.delete(key)
+        else:
+            self.store.delete(key)
+
+    def flush(self):
+        if self.store is not None:
+            self.ix.sync()
+
+    def key_of(self, row):
+        if self.store is None:
+            return self.ix.keys[row]
+        res = self.store.mirror_results(np.array([row], dtype=np.int32), "", "", gen=self.ix.generation)[0]
+        return json.loads(res)["results"][0]["key"]
+
+    # -- mirror operations
+    def check(self):
+        assert_mirror_matches_index(self.ix, self.k, self.read, self.asked, self.plans)
+        self.checks += 1
+
+    def sync(self, rank_cols=()):
+        self.flush()
+        self.ix.mirror.sync(self.k, rank_cols)
+        self.asked = sorted(set(rank_cols))
+        self.check()
+
+    def prog(self, flt):
+        self.flush()
+        return flt if isinstance(flt, Program) else self.ix.compile_cached(flt)
+
+    @staticmethod
+    def _range_cols(prog):
+        return sorted(set(prog.code[prog.code[:, 0] == OP_RANGE, 1].tolist()))
+
+    def select(self, flt):
+        """``program`` + the kernels' select over the mirror's buffers == the host executor."""
+        ix, prog = self.ix, self.prog(flt)
+        m, code, bitmaps = ix.mirror.program(prog, self.k)
+        self.asked = self._range_cols(prog)
+        self.check()
+        got = self.read(self.k.select(m.table, m.live, ix.cap, ix.n, code, bitmaps))
+        want = ix.select_numpy(prog)
+        assert np.array_equal(got, want), (flt if not isinstance(flt, Program) else "program", got.size, want.size)
+        return got
+
+    def sort_plan(self, sort):
+        self.flush()
+        plan = self.ix.mirror.sort_plan(sort, self.k)
+        assert plan is not None
+        self.plans.append(sort)
+        self.check()
+        return plan
+
+    def page(self, flt, sort, offset, limit):
+        """``page_gpu`` == the host's page at the same offset (rows and token)."""
+        ix, prog = self.ix, self.prog(flt)
+        res = ix.page_gpu(prog, sort, self.k, offset, limit)
+        assert res is not None
+        self.asked = self._range_cols(prog)
+        self.plans.append(sort)
+        self.check()
+        q = {"filter": flt, "page": {"limit": limit, **({"token": str(offset)} if offset else {})},
+             **({"sort": sort} if sort else {})}
+        rows, token = ix.query_rows(q)
+        assert res[0].tolist() == rows.tolist() and res[1] == token, (sort, offset, limit)
+        return res
+
+    def order(self, flt, sort):
+        ix, prog = self.ix, self.prog(flt)
+        rows = ix.select_gpu(prog, self.k, on_device=True)
+        got = ix.order_gpu(rows, sort, self.k)
+        self.asked = []
+        self.plans.append(sort)
+        self.check()
+        assert self.read(got).tolist() == ix.order(ix.select_numpy(prog), sort).tolist()
+
+    def warm(self):
+        self.flush()
+        self.ix.warm(self.k)
+        self.asked = sorted(set(self.ix.mirror.rank_cols))
+        self.check()
+
+
+PATHS = ["b", "m", "c", "d"]
+F_RANGE2 = {"AND": [{"GTE": {"m": "m010"}}, {"LT": {"d": 30}}]}    # two range leaves
+F_RANGE1 = {"LT": {"d": 30}}
+F_RANGE_M = {"GTE": {"m": "m010"}}
+F_EQ = {"EQ": {"b": False}}
+F_PAGE = {"AND": [{"EQ": {"b": False}}, {"LT": {"d": 40}}]}
+SORTS = [None, [{"key": "c"}], [{"key": "d", "order": "DESC"}, {"key": "c"}]]
+SEEDS = [1, 2, 3]
+
+
+def _doc(rnd, stamps=40_000):
+    """b: 2-bit codes; m, d: one byte; c: up to ``stamps`` timestamps in no order (two bytes,
+    every new one lands inside the sort order and moves the ranks of the others)."""
+    t = rnd.randrange(stamps)
+    d = {"b": rnd.choice([True, False, None]), "m": f"m{rnd.randrange(40):03d}", "d": rnd.randrange(50),
+         "c": f"2025-01-{1 + t // 1440:02d}T{t // 60 % 24:02d}:{t % 60:02d}:00", "e": rnd.randrange(5)}
+    if rnd.random() < 0.06:
+        del d[rnd.choice(PATHS)]
+    return d
+
+
+def _make(kernels, read, backend, capacity=3 * TILE, paths=PATHS):
+    if backend == "docs":
+        return Run(ColumnarIndex(paths, capacity=capacity), kernels, read)
+    store = native.load().DocStore()
+    return Run(ColumnarIndex.from_native(store, paths), kernels, read, store)
+
+
+# ------------------------------------------------------------------ a. appends
+def history_appends(kernels, read, seed, backend="docs"):
+    """Batches whose ends fall on every residue mod 16 (so mod 4 too: the 2-bit edge bytes and
+    the liveness tail words), synced after one batch or after several, and a sync with nothing new."""
+    rnd = random.Random(seed)
+    run = _make(kernels, read, backend)
+    ix = run.ix
+    sizes = [1, 3, 4097, 7, 16, 15] + [17] * 16 + [20_000 - 272, 5, 64, 1]
+    assert sum(sizes) <= 3 * TILE
+    cols = [ix.col_of["m"], ix.col_of["d"], ix.col_of["b"]]
+    ends, made = set(), 0
+    for size in sizes:
+        for _ in range(size):
+            run.put(f"k{made}", _doc(rnd))
+            made += 1
+        if size != 17 and size != 1 and rnd.random() < 0.4:
+            continue  # several batches go up together
+        ends.add(made % 16)
+        how = rnd.randrange(5)
+        if how == 0:
+            run.sync()
+        elif how == 1:
+            run.sync(cols[:2])
+        elif how == 2:
+            run.sync(cols)
+        else:
+            run.select([F_RANGE2, F_EQ][how - 3])
+        if rnd.random() < 0.3:
+            run.sync(rnd.choice([(), cols]))  # nothing new
+    assert ends == set(range(16)) and ix.n == made
+    run.sync(cols)
+    uploads = getattr(kernels, "uploads", None)
+    run.sync(cols)  # nothing new
+    assert uploads is None or kernels.uploads == uploads  # ... and nothing sent
+    for f in (F_RANGE2, F_EQ, F_RANGE1, {}):
+        run.select(f)
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_appends(seed):
+    history_appends(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_appends(gpu, seed):
+    history_appends(*gpu, seed)
+
+
+# ------------------------------------------------------------------ b. tombstones and updates
+def _live_in_tile(ix, t):
+    return np.nonzero(ix.live[t * TILE:min((t + 1) * TILE, ix.n)])[0] + t * TILE
+
+
+def history_tombstones(kernels, read, seed, backend="docs", rounds=4):
+    """Deletes in tiles no filter singles out, updates that kill the row a zone map points at and
+    land in another tile, deletes and appends between two syncs."""
+    rnd = random.Random(seed)
+    run = _make(kernels, read, backend)
+    ix = run.ix
+    made = 20_500
+    for i in range(made):
+        run.put(f"k{i}", _doc(rnd))
+    run.sync()
+    for sort in SORTS:  # the zone maps exist from here on
+        run.page(F_PAGE, sort, 0, 50)
+    cols = [ix.col_of["m"], ix.col_of["d"]]
+    for r in range(rounds):
+        sort = SORTS[(r + seed) % 3]
+        # deletes in the middle tile, the row its zone points at among them
+        run.flush()
+        victims = rnd.sample(_live_in_tile(ix, 1).tolist(), 25) + [int(_zone_reference(ix, sort)[1])]
+        for key in [run.key_of(v) for v in set(victims)]:
+            run.delete(key)
+        run.sync(cols if r % 2 else ())
+        run.select(F_EQ)
+        # an update: the old row (tile 0's argmin) dies, the new one lands in the last tile
+        run.flush()
+        old = int(_zone_reference(ix, sort)[0])
+        run.put(run.key_of(old), _doc(rnd))
+        run.flush()
+        assert not ix.live[old] and (ix.n - 1) // TILE != old // TILE
+        if r % 2:
+            run.warm()
+        run.page(F_PAGE, sort, 0, 50)
+        # a delete and appends in one interval: the whole liveness mask goes up, not only its tail
+        run.delete(run.key_of(int(rnd.choice(_live_in_tile(ix, r % 2).tolist()))))
+        for _ in range(rnd.choice([1, 2, 3, 5, 19])):
+            run.put(f"k{made}", _doc(rnd))
+            made += 1
+        if r % 2:
+            run.sync(cols)
+        else:
+            run.select(F_RANGE2)
+        run.warm()
+        for s in SORTS:
+            run.page(F_PAGE, s, 50, 20)
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_tombstones_and_updates(seed):
+    history_tombstones(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_tombstones_and_updates(gpu, seed):
+    history_tombstones(*gpu, seed)
+
+
+# ------------------------------------------------------------------ c. width growth
+def history_width_growth(kernels, read, seed):
+    """Column v grows through 3 -> 4, 254 -> 255 and 65,534 -> 65,535 values under a range leaf
+    (its values arrive in no order: every new one moves the ranks of the others); column o keeps
+    its width.  Returns the run (the last state holds a 4-byte column)."""
+    rnd = random.Random(seed)
+    run = _make(kernels, read, "docs", capacity=9 * TILE, paths=["v", "o"])
+    ix, m = run.ix, run.ix.mirror
+    v, o = ix.col_of["v"], ix.col_of["o"]
+    for i in range(10):  # o's dictionary is complete (one byte) before v begins
+        run.put(f"o{i}", {"o": f"o{i}"})
+    names = [f"v{j:05d}" for j in range(65_535)]
+    rnd.shuffle(names)
+    flt = {"AND": [{"GTE": {"v": "v30000"}}, {"NEQ": {"o": "o3"}}]}
+    stops = sorted({2, 3, 4, 100, 101, 254, 255, 256, 65_534, 65_535} | set(rnd.sample(range(300, 65_000), 3)))
+    rank_width = {2: 1, 3: 1, 4: 1, 100: 1, 101: 1, 254: 1, 255: 2, 256: 2, 65_534: 2, 65_535: 4}
+    made, before = 0, None
+    for size in stops:
+        while made < size:
+            run.put(f"k{ix.n}", {"v": names[made], "o": f"o{rnd.randrange(10)}"})
+            made += 1
+            if rnd.random() < 0.03:
+                run.put(f"k{ix.n}", {"o": f"o{rnd.randrange(10)}"})  # v missing
+        assert len(ix.columns[v].values) == size and len(ix.columns[o].values) == 10
+        run.select(flt)
+        rc = m.ranks[v]
+        assert m.widths[v] == width_for(size) and m.widths[o] == 1 and rc.w == rank_width.get(size, 2)
+        if before is not None:
+            was, t, table, col = before
+            if size == was + 1 and rank_width[size] == rank_width[was]:
+                # a new value, the same rank width: re-encoded from row 0 into the same buffer
+                # (the invariant has compared every row with the new ranks)
+                assert rc.t is t and rc.t.data_ptr() == t.data_ptr()
+                assert (m.table is table) == (m.cols[v] is col)  # the cached table while the source stays
+            elif size == was + 1:
+                assert rc.t is not t and rc.t.data_ptr() != t.data_ptr() and m.table is not table  # a new width
+        before = (size, rc.t, m.table, m.cols[v])
+        run.select(flt)  # nothing new
+    for batch in (1, 37):  # appends to the 4-byte column (its codes are the index's own ids)
+        for _ in range(batch):
+            run.put(f"k{ix.n}", {"v": names[rnd.randrange(made)], "o": f"o{rnd.randrange(10)}"})
+        run.select(flt)
+    assert m.ranks[v].t is before[1] and m.cols[v] is before[3]
+    assert ix.n <= ix.cap == 9 * TILE  # no growth: every upload above was incremental
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_width_growth(seed):
+    run = history_width_growth(*_host(), seed)
+    ix = run.ix
+    v = ix.col_of["v"]
+    assert ix.mirror.widths[v] == 4 and np.shares_memory(ix.codes(v, 0, ix.cap, 4), ix.ids)
+    # the stand-in owns its memory: a 4-byte column is the one the old emulation aliased
+    assert not np.shares_memory(ix.mirror.cols[v].numpy(), ix.ids)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_width_growth(gpu, seed):
+    history_width_growth(*gpu, seed)
+
+
+# ------------------------------------------------------------------ d. layout changes
+def _after_layout_change(run, flt, prog, rank_col, old_rc):
+    """The mirror's rank columns were rebuilt, the invariant holds, and the program compiled
+    before the change (with its cached device copy) still selects the right rows."""
+    ix = run.ix
+    run.select(prog)
+    rc = ix.mirror.ranks[rank_col]
+    assert rc is not old_rc and rc.t is not old_rc.t and rc.t.numel() == ix.cap
+    assert np.array_equal(ix.select_numpy(prog), ix.select_numpy(ix.compile(flt)))
+    return rc
+
+
+def history_layout(kernels, read, seed):
+    rnd = random.Random(seed)
+    run = _make(kernels, read, "docs", capacity=TILE)
+    ix = run.ix
+    made = 0
+
+    def append(upto):
+        nonlocal made
+        while ix.n < upto:
+            run.put(f"k{made}", _doc(rnd, stamps=500))
+            made += 1
+
+    append(TILE - 2)
+    prog = ix.compile_cached(F_RANGE2)
+    col = ix.col_of["m"]
+    run.select(prog)
+    rc = ix.mirror.ranks[col]
+    assert prog.device is not None
+    for tile_end in (TILE, 2 * TILE):  # the capacity doubles across 8192 and 16384
+        append(tile_end - 2)
+        run.select(prog)
+        rc = ix.mirror.ranks[col]
+        append(tile_end + 5)
+        assert ix.cap == 2 * tile_end and ix.compile_cached(F_RANGE2) is prog
+        rc = _after_layout_change(run, F_RANGE2, prog, col, rc)
+    for key in rnd.sample(range(made), 500):
+        run.delete(f"k{key}")
+    run.select(prog)
+    run.page(F_PAGE, SORTS[1], 0, 50)
+    n = ix.n
+    ix.compact()
+    assert ix.n == n - 500
+    rc = _after_layout_change(run, F_RANGE2, prog, col, rc)
+    run.page(F_PAGE, SORTS[1], 0, 50)
+    keys = [ix.keys[r] for r in np.nonzero(ix.live[:ix.n])[0].tolist()]
+    rnd.shuffle(keys)
+    n = ix.n
+    for i, key in enumerate(keys[:TILE + 1]):  # more than a tile of tombstones, over half the rows
+        run.delete(key)
+        if i == 4000:
+            run.select(prog)  # tombstones go up, then the layout changes
+    assert ix.n < n - TILE and ix._dead == 0  # _maybe_compact ran
+    rc = _after_layout_change(run, F_RANGE2, prog, col, rc)
+    assert ix.add_column("e") == len(PATHS)
+    rc = _after_layout_change(run, F_RANGE2, prog, col, rc)
+    run.select({"AND": [{"GT": {"e": 1}}, F_RANGE1]})
+    for s in SORTS:
+        run.page(F_PAGE, s, 0, 50)
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_layout_changes(seed):
+    history_layout(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_layout_changes(gpu, seed):
+    history_layout(*gpu, seed)
+
+
+def history_source_backed_add_column(kernels, read, seed):
+    """``add_column`` on a ``from_source`` index re-encodes every column from the store."""
+    rnd = random.Random(seed)
+    store = native.load().DocStore()
+    docs = {}
+
+    def put(key, doc):
+        docs[key] = doc
+        store.set(key, json.dumps(doc))
+
+    for i in range(TILE + 300):
+        put(f"k{i}", _doc(rnd, stamps=500))
+    ix = ColumnarIndex.from_source(lambda paths: store.encode_columns("", paths), PATHS)
+    run = Run(ix, kernels, read)
+    prog = ix.compile_cached(F_RANGE2)
+    col = ix.col_of["m"]
+    run.select(prog)
+    for i in range(200):  # mirrored writes, as the accelerator hooks apply them
+        key = f"k{rnd.randrange(TILE)}"
+        put(key, _doc(rnd, stamps=500))
+        run.put(key, docs[key])
+    run.select(prog)
+    rc = ix.mirror.ranks[col]
+    assert ix.add_column("e") == len(PATHS) and ix.docs is None
+    _after_layout_change(run, F_RANGE2, prog, col, rc)
+    run.select({"AND": [{"GT": {"e": 1}}, F_RANGE1]})
+    run.page(F_PAGE, SORTS[2], 0, 50)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_source_backed_add_column(seed):
+    history_source_backed_add_column(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_source_backed_add_column(gpu, seed):
+    history_source_backed_add_column(*gpu, seed)
+
+
+# ------------------------------------------------------------------ e. rank-slot remapping
+def history_rank_slots(kernels, read, seed):
+    """Programs with no, one and two range leaves in turn: a column's rank copy changes its row of
+    the descriptor table with the company it keeps, and ``Program.device`` is cached by slots."""
+    rnd = random.Random(seed)
+    run = _make(kernels, read, "docs")
+    ix = run.ix
+    made = 0
+    for _ in range(TILE + 500):
+        run.put(f"k{made}", _doc(rnd, stamps=500))
+        made += 1
+    filters = [F_EQ, F_RANGE1, F_RANGE2, F_RANGE_M, {"AND": [{"LT": {"b": True}}, F_RANGE1]}]
+    progs = [ix.compile_cached(f) for f in filters]
+    m_col, d_col = ix.col_of["m"], ix.col_of["d"]
+    seen = set()
+    for order in ([0, 1, 2], [2, 1, 0], [1, 3, 2, 0, 4, 1], rnd.sample(range(5), 5), rnd.sample(range(5), 5)):
+        for i in order:
+            assert ix.compile_cached(filters[i]) is progs[i]  # the dictionaries hold: the cached program
+            run.select(progs[i])
+            seen.add((i, tuple(sorted(ix.mirror.rank_slot.items())) if run.asked else ()))
+        for _ in range(rnd.choice([0, 3, 16, 33])):
+            run.put(f"k{made}", _doc(rnd, stamps=500))
+            made += 1
+    # d's rank copy sat in two different slots (alone, behind b's, behind m's)
+    assert len({dict(s).get(d_col) for _, s in seen if s}) >= 2 and any(dict(s).get(m_col) for _, s in seen)
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_rank_slot_remapping(seed):
+    history_rank_slots(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_rank_slot_remapping(gpu, seed):
+    history_rank_slots(*gpu, seed)
+
+
+# ------------------------------------------------------------------ f. zones and paging
+def history_paging(kernels, read, seed):
+    """``page_gpu`` under three sorts on one index, writes between the pages (updates that move a
+    row to another tile, deletes, timestamps that land inside the order): every page equals the
+    host's page at its offset, and an undisturbed walk concatenates to the full host order."""
+    rnd = random.Random(seed)
+    run = _make(kernels, read, "docs")
+    ix = run.ix
+    made = 20_000
+    for i in range(made):
+        run.put(f"k{i}", _doc(rnd, stamps=3000))
+    flt = {"AND": [{"EQ": {"b": False}}, {"LT": {"d": 40}}]}
+    for r in range(2):
+        for sort in SORTS:
+            q = {"filter": flt, **({"sort": sort} if sort else {})}
+            full = ix.query_rows(q)[0].tolist()
+            assert 900 < len(full) < TILE
+            got, token = [], None
+            while True:  # an undisturbed walk
+                rows, token = run.page(flt, sort, int(token or 0), 900)
+                got += rows.tolist()
+                if token is None:
+                    break
+            assert got == full
+            token = None
+            for _ in range(4):  # pages with writes between them
+                rows, token = run.page(flt, sort, int(token or 0), rnd.choice([1, 7, 100]))
+                for _ in range(12):
+                    i = rnd.randrange(made)
+                    if rnd.random() < 0.25:
+                        run.delete(f"k{i}")
+                    else:  # an update: a timestamp never seen before, inside the order
+                        run.put(f"k{i}", dict(_doc(rnd), c=f"2025-01-{1 + rnd.randrange(3):02d}T00:00:{rnd.randrange(60):02d}.5"))
+                old = int(_zone_reference(ix, sort)[rnd.randrange(2)])  # the row a zone points at
+                run.put(ix.keys[old], _doc(rnd, stamps=3000))
+                if rnd.random() < 0.3:
+                    run.warm()
+                if token is None:
+                    break
+        run.order(flt, SORTS[2])
+    return run
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_zones_and_paging(seed):
+    history_paging(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_zones_and_paging(gpu, seed):
+    history_paging(*gpu, seed)
+
+
+# ------------------------------------------------------------------ g. the native mirror
+def history_native(kernels, read, seed):
+    """Appends, tombstones and a new column over ``ColumnarIndex.from_native``: ``sync`` reports
+    the store's kills and appends to the mirror by its own path."""
+    run = history_appends(kernels, read, seed, backend="native")
+    assert run.store is not None and run.ix.native is run.store
+    run = history_tombstones(kernels, read, seed, backend="native", rounds=2)
+    ix = run.ix
+    prog = ix.compile_cached(F_RANGE2)
+    run.select(prog)
+    col, gen = ix.col_of["m"], ix.generation
+    rc = ix.mirror.ranks[col]
+    ix.ensure_columns(["e"])  # a new column: a new mirror generation, a full reload
+    assert ix.generation != gen and len(ix.columns) == len(PATHS) + 1
+    run.plans = []
+    run.select(ix.compile_cached(F_RANGE2))
+    assert ix.mirror.ranks[col] is not rc
+    run.select({"AND": [{"GT": {"e": 1}}, F_RANGE1]})
+    for s in SORTS:
+        run.page(F_PAGE, s, 0, 50)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_native_mirror(seed):
+    history_native(*_host(), seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+def test_gpu_native_mirror(gpu, seed):
+    history_native(*gpu, seed)
+
+
+# ------------------------------------------------------------------ the stand-in's other answers
+def test_stand_in_grouped_and_ordered_queries_match_the_host():
+    """``group_count``, ``scan_group``, ``sort_keys`` and ``order`` of the stand-in, through the
+    index's own callers, against the host paths."""
+    rnd = random.Random(4)
+    kernels, read = _host()
+    run = _make(kernels, read, "docs")
+    ix = run.ix
+    for i in range(TILE + 77):
+        run.put(f"k{i}", _doc(rnd, stamps=500))
+    for i in rnd.sample(range(TILE + 77), 300):
+        run.delete(f"k{i}")
+    prog = ix.compile_cached(F_RANGE2)
+    assert ix.group_count_gpu(prog, "m", kernels) == ix.group_count_numpy(prog, "m")
+    q = {"filter": F_RANGE1, "groupBy": ["b", "m"], "aggregate": [{"op": "COUNT"}, {"op": "SUM", "key": "d"},
+                                                                   {"op": "MAX", "key": "c"}]}
+    assert ix.aggregate(q, kernels) == ix.aggregate(q)
+    for sort in SORTS:
+        for page in ({}, {"limit": 9000}):  # past the page path: select + order
+            qq = {"filter": F_PAGE, "page": page, **({"sort": sort} if sort else {})}
+            assert ix.query(qq, kernels) == ix.query(qq)
+        run.order(F_PAGE, sort)
