@@ -244,7 +244,8 @@ class CollectionAccelerator:
                 self.stats[key] = round(v, 3)
             return out
 
-    def aggregate(self, q: dict[str, Any], prefix: str, store, hist: bool = False) -> dict[str, Any] | None:
+    def aggregate(self, q: dict[str, Any], prefix: str, store, hist: bool = False,
+                  partial: bool = False) -> dict[str, Any] | None:
         """Grouped aggregates (``ColumnarIndex.aggregate``) from the mirror at its sync point, or
         None to let the caller aggregate the native engine's documents.  Always a scan, so the
         hash-index shortcut of ``query`` does not apply; no row goes back to the store.
@@ -267,7 +268,7 @@ class CollectionAccelerator:
                     flt = {"AND": [{"EQ": {PREFIX_PATH: prefix}}, flt]} if flt else {"EQ": {PREFIX_PATH: prefix}}
                 k = self.kernels()
                 try:
-                    out = self.index.aggregate({**q, "filter": flt}, k, hist)
+                    out = self.index.aggregate({**q, "filter": flt}, k, hist, partial)
                 except Unsupported:  # this request only: the mirror stays
                     self.stats["fallback"] += 1
                     return None

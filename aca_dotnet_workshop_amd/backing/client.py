@@ -124,10 +124,13 @@ class BackingClient:
         return r.body
 
     async def doc_aggregate(self, account: str, db: str, coll: str, query: bytes, prefix: str = "",
-                            hist: bool = False) -> bytes:
+                            hist: bool = False, partial: bool = False) -> bytes:
         """Grouped aggregates (``{"filter", "groupBy", "aggregate"}`` -> ``{"groups": [...]}``);
-        ``hist``: the raw histograms per aggregate key instead of the reduced values."""
-        args = {**({"prefix": prefix} if prefix else {}), **({"project": "hist"} if hist else {})}
+        ``hist``: the raw histograms per aggregate key instead of the reduced values;
+        ``partial``: the form a merge of several stores needs at the least size -- [count, min,
+        max] for the keys of which no more is asked, histograms for the others."""
+        project = "hist" if hist else "partial" if partial else ""
+        args = {**({"prefix": prefix} if prefix else {}), **({"project": project} if project else {})}
         path = f"{self._coll(account, db, coll)}/aggregate" + ("?" + urlencode(args) if args else "")
         r = await self._req("POST", path, query, {"Content-Type": "application/json"}, what="state aggregate")
         return r.body

@@ -201,24 +201,27 @@ class BackingServices:
         span.end()
         return 200, body, [("x-tt-handler-end-mono", f"{time.monotonic():.6f}")]
 
-    def run_aggregate(self, account: str, db: str, coll: str, raw: bytes, prefix: str, hist: bool) -> tuple[int, bytes]:
+    def run_aggregate(self, account: str, db: str, coll: str, raw: bytes, prefix: str, hist: bool,
+                      partial: bool = False) -> tuple[int, bytes]:
         """Grouped aggregates of the collection, after admission (``ops.columnar.parse_aggregate``
         has the request): from the columnar / GPU accelerator, or -- accelerator off, a small or
         a TTL collection, a filter the mirror does not take -- over the documents the native
         engine's query returns, reduced by the same ``AggGroups`` / ``reduce_hist``.  ``hist``:
-        the raw histograms (a shard's share of a partitioned collection).  Returns (200, result
-        JSON) -- the result-size RU are debited here -- or (400, the error).  Blocking."""
+        the raw histograms; ``partial``: [count, min, max] for the keys of which no more is asked,
+        histograms for the others (either is a shard's share of a partitioned collection).
+        Returns (200, result JSON) -- the result-size RU are debited here -- or (400, the error).
+        Blocking."""
         s = self.store(account, db, coll)
         try:
             q = json.loads(raw.decode("utf-8") if raw else "{}")
             spec = parse_aggregate(q)
-            res = self.accel(account, db, coll).aggregate(q, prefix, s, hist)
+            res = self.accel(account, db, coll).aggregate(q, prefix, s, hist, partial)
             if res is None:
                 docs = json.loads(s.query(json.dumps({"filter": spec.filter} if spec.filter else {}), prefix, False))
                 groups = AggGroups(spec)
                 for r in docs["results"]:
                     groups.add_doc(r["data"])
-                res = groups.response(hist)
+                res = groups.response(hist, partial)
         except ValueError as ex:
             return 400, str(ex).encode()
         body = json.dumps(res, separators=(",", ":")).encode()
@@ -401,13 +404,16 @@ class BackingServices:
             s = st(req, "cosmos.read")
             # ?project=hist: per group the raw (value, rows) histogram of each aggregate key --
             # a shard's share, which the partitioned client adds up before reducing once
-            hist = (req.query_get("project", "") or "").lower() == "hist"
+            # ?project=partial: the same with [count, min, max] in place of the histogram of a key
+            # of which only COUNT / MIN / MAX are asked (a timestamp's histogram is the column)
+            project = (req.query_get("project", "") or "").lower()
+            hist = project == "hist"
             if (t := throttled(req, s, s.query_ru(0), 2)) is not None:
                 return t
             p = req.path_params
             status, body = await asyncio.get_running_loop().run_in_executor(
                 self.query_pool, self.run_aggregate, p["account"], p["db"], p["coll"], req.body,
-                req.query_get("prefix", "") or "", hist)
+                req.query_get("prefix", "") or "", hist, project == "partial")
             if status != 200:
                 return problem(status, detail=body.decode("utf-8", "replace"))
             return Response(body, 200, None, "application/json")

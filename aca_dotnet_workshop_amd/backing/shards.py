@@ -279,21 +279,24 @@ class ShardedBackingClient:
         pages = await asyncio.gather(*(one(i) for i in range(self.n)))
         return json.dumps(merge_pages(q, list(pages), offsets), separators=(",", ":")).encode()
 
-    async def doc_aggregate(self, account, db, coll, query: bytes, prefix: str = "", hist: bool = False) -> bytes:
-        """Every shard's raw histograms, the counts of equal groups and values added, reduced
-        once: the answer of one store over the same documents (an average of averages or a
-        sum of rounded sums would not be)."""
+    async def doc_aggregate(self, account, db, coll, query: bytes, prefix: str = "", hist: bool = False,
+                            partial: bool = False) -> bytes:
+        """Every shard's partial answer -- raw histograms, and [count, min, max] for the keys of
+        which no more is asked (``project=partial``; with ``hist`` histograms throughout) -- the
+        counts of equal groups and values added, the extrema merged, reduced once: the answer of
+        one store over the same documents (an average of averages or a sum of rounded sums
+        would not be)."""
         from ..ops.columnar import AggGroups, parse_aggregate
         try:
             spec = parse_aggregate(json.loads(query or b"{}"))
         except ValueError as ex:
             raise BackingError(400, str(ex).encode(), "state aggregate") from None
-        parts = await asyncio.gather(*(c.doc_aggregate(account, db, coll, query, prefix, hist=True)
+        parts = await asyncio.gather(*(c.doc_aggregate(account, db, coll, query, prefix, hist=hist, partial=not hist)
                                        for c in self.shards))
         groups = AggGroups(spec)
         for body in parts:
             groups.add_response(json.loads(body))
-        return json.dumps(groups.response(hist), separators=(",", ":")).encode()
+        return json.dumps(groups.response(hist, partial), separators=(",", ":")).encode()
 
     async def doc_stats(self, account, db, coll):
         parts = await asyncio.gather(*(c.doc_stats(account, db, coll) for c in self.shards))

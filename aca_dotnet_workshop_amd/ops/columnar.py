@@ -141,7 +141,9 @@ def filter_paths(f: Any) -> list[str]:
 # -- grouped aggregates: the semantics, shared by every execution path -----------------------
 # GPU (hip/group_agg.hip), CPU columnar, the native engine's documents (backing/server.py) and
 # the shard merge (backing/shards.py) all reduce to per-group histograms of (value, row count)
-# held in ``AggGroups`` and finish in ``reduce_hist``: one definition, one answer.
+# held in ``AggGroups`` and finish in ``reduce_hist``: one definition, one answer.  A key of which
+# only COUNT / MIN / MAX are asked may instead arrive as per-group extrema (hip/group_extrema.hip,
+# ``ColumnarIndex.extrema_numpy``, a shard's ``project=partial``), merged by ``compare``.
 AGG_OPS = ("COUNT", "SUM", "AVG", "MIN", "MAX")
 MAX_GROUP_BY = 2
 
@@ -218,10 +220,22 @@ def parse_aggregate(q: Any) -> AggSpec:
     return AggSpec(flt or None, list(group_by), aggs, list(dict.fromkeys(k for _, k in aggs if k is not None)))
 
 
+EXTREMA_OPS = frozenset(("COUNT", "MIN", "MAX"))
+
+
+def extrema_keys(spec: AggSpec) -> list[str]:
+    """The aggregate keys of which only COUNT, MIN and MAX are asked: three numbers per group
+    answer them (``AggGroups.add_extrema``), no histogram is needed."""
+    return [k for k in spec.keys if all(op in EXTREMA_OPS for op, kk in spec.aggs if kk == k)]
+
+
 class AggGroups:
     """Per group (the group-by values, a missing path apart from JSON null): its row count and,
-    per aggregate key, the histogram of the key's values.  Counts of equal groups and values
-    (``vkey``) add, so partial answers -- launches, shards -- merge by adding themselves."""
+    per aggregate key, the histogram of the key's values -- or, for a key of ``extrema_keys``,
+    its extrema: [rows where it is defined, smallest value, largest value].  Counts of equal
+    groups and values (``vkey``) add and extrema merge by ``compare``, so partial answers --
+    launches, shards -- merge by adding themselves.  Which form a key is held in follows from
+    the request and the path taken, the same for every part of one answer."""
 
     def __init__(self, spec: AggSpec) -> None:
         self.spec = spec
@@ -234,8 +248,25 @@ class AggGroups:
         g = self.groups.get(gk)
         if g is None:
             g = self.groups[gk] = {"values": tuple(v if v is _MISSING else _canon(v) for v in gvals), "count": 0,
-                                   "hist": {k: {} for k in self.spec.keys}}
+                                   "hist": {k: {} for k in self.spec.keys}, "ext": {}}
         return g
+
+    def add_extrema(self, gvals: tuple, key: str, count: int, lo_value: Any = None, hi_value: Any = None) -> None:
+        """``count`` rows of the group hold ``key``, their values between ``lo_value`` and
+        ``hi_value`` (both among them); nothing when ``count`` is 0."""
+        if not count:
+            return
+        lo, hi = _canon(lo_value), _canon(hi_value)
+        ext = self._group(gvals)["ext"]
+        e = ext.get(key)
+        if e is None:
+            ext[key] = [int(count), lo, hi]
+            return
+        e[0] += int(count)
+        if compare(lo, e[1]) < 0:
+            e[1] = lo
+        if compare(hi, e[2]) > 0:
+            e[2] = hi
 
     def add_rows(self, gvals: tuple, n: int) -> None:
         self._group(gvals)["count"] += int(n)
@@ -258,17 +289,32 @@ class AggGroups:
                 self.add_value(gvals, k, v, 1)
 
     def add_response(self, res: dict[str, Any]) -> None:
-        """A ``project=hist`` answer of another store (a shard)."""
+        """A ``project=hist`` or ``project=partial`` answer of another store (a shard)."""
         for g in res["groups"]:
             gvals = tuple(g["group"].get(p, _MISSING) for p in self.spec.group_by)
             self.add_rows(gvals, g["count"])
-            for k, pairs in g["hist"].items():
+            for k, pairs in g.get("hist", {}).items():
                 for v, c in pairs:
                     self.add_value(gvals, k, v, c)
+            for k, e in g.get("ext", {}).items():
+                self.add_extrema(gvals, k, *e)
 
-    def response(self, hist: bool = False) -> dict[str, Any]:
+    def _extrema(self, g: dict[str, Any], key: str) -> list | None:
+        """[count, min, max] of ``key`` in group ``g`` from its extrema when it holds them, else
+        from its histogram; None without a defined value."""
+        e = g["ext"].get(key)
+        if e is not None:
+            return e
+        r = reduce_hist(g["hist"][key].values(), ("COUNT", "MIN", "MAX"))
+        return [r["COUNT"], r["MIN"], r["MAX"]] if r["COUNT"] else None
+
+    def response(self, hist: bool = False, partial: bool = False) -> dict[str, Any]:
         """The route's answer: groups sorted by their values (``compare``, a missing path
-        first); ``hist``: the raw histograms per aggregate key instead of the reduced values."""
+        first); ``hist``: the raw histograms per aggregate key instead of the reduced values;
+        ``partial`` (without ``hist``): what another ``AggGroups`` merges (``add_response``)
+        at the least size -- ``"ext": {key: [count, min, max]}`` for the keys of
+        ``extrema_keys`` (``[0]``: no defined value) and ``"hist"`` for the others."""
+        ext_keys = set() if hist else set(extrema_keys(self.spec))
         def cmp(a: dict, b: dict) -> int:
             for x, y in zip(a["values"], b["values"]):
                 if x is _MISSING or y is _MISSING:
@@ -284,13 +330,20 @@ class AggGroups:
                 continue
             o: dict[str, Any] = {"group": {p: v for p, v in zip(self.spec.group_by, g["values"]) if v is not _MISSING},
                                  "count": g["count"]}
-            if hist:
+            if hist or partial:
                 o["hist"] = {k: sorted(([v, c] for v, c in h.values()),
                                        key=functools.cmp_to_key(lambda a, b: compare(a[0], b[0])))
-                             for k, h in g["hist"].items()}
+                             for k, h in g["hist"].items() if k not in ext_keys}
+                if not hist:
+                    o["ext"] = {k: self._extrema(g, k) or [0] for k in self.spec.keys if k in ext_keys}
             else:
-                red = {k: reduce_hist(h.values(), [op for op, kk in self.spec.aggs if kk == k])
-                       for k, h in g["hist"].items()}
+                red = {}
+                for k, h in g["hist"].items():
+                    ops = [op for op, kk in self.spec.aggs if kk == k]
+                    if k in g["ext"]:
+                        red[k] = {op: v for op, v in zip(("COUNT", "MIN", "MAX"), g["ext"][k]) if op in ops}
+                    else:
+                        red[k] = reduce_hist(h.values(), ops)
                 aggs = []
                 for op, k in self.spec.aggs:
                     if k is None:
@@ -1152,7 +1205,37 @@ class ColumnarIndex:
     # ``np.unique`` (no array of all cells).  The device's own cap is ``tt_group_max_cells()``.
     HOST_MAX_CELLS = 1 << 22
 
-    def aggregate(self, q: dict[str, Any], kernels=None, hist: bool = False) -> dict[str, Any]:
+    # An aggregate key of which only COUNT / MIN / MAX are asked leaves the histogram for the
+    # per-group extrema (``hip/group_extrema.hip``, ``extrema_numpy``) when its histogram would
+    # have more cells than this; with kernels, than the smaller of this and the device's cap.
+    EXTREMA_FROM_CELLS = 1 << 22
+
+    def _dict_size(self, col: int) -> int:
+        """The dictionary size of a column as the aggregate planner sees it."""
+        return len(self.columns[col].values)
+
+    def extrema_numpy(self, rows: np.ndarray, gcols: list[int], gdims: list[int],
+                      kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Host twin of ``hip/group_extrema.hip`` over the selected ``rows``: (cells with a
+        defined value of column ``kc``, their row counts, smallest and largest ``rank << 32 |
+        row``), the cell of a row as in ``aggregate``'s histograms of the group columns."""
+        ids = self.ids[kc, rows]
+        rows, ids = rows[ids >= 0], ids[ids >= 0]
+        cell = np.zeros(rows.size, dtype=np.int64)
+        for c, d in zip(gcols, gdims):
+            g = self.ids[c, rows]
+            cell = cell * (d + 1) + np.where(g < 0, d, g)
+        ranks = self.columns[kc].ranks()[ids] if ids.size else np.zeros(0, dtype=np.int64)
+        key = (ranks.astype(np.uint64) << np.uint64(32)) | rows.astype(np.uint64)
+        order = np.lexsort((key, cell))  # by cell, then by key: a cell's extrema at its ends
+        cell, key = cell[order], key[order]
+        if not cell.size:
+            return cell, cell, key, key
+        starts = np.flatnonzero(np.concatenate([[True], cell[1:] != cell[:-1]]))
+        ends = np.concatenate([starts[1:], [cell.size]])
+        return cell[starts], ends - starts, key[starts], key[ends - 1]
+
+    def aggregate(self, q: dict[str, Any], kernels=None, hist: bool = False, partial: bool = False) -> dict[str, Any]:
         """Grouped aggregates over the filtered collection (``parse_aggregate`` has the request,
         ``AggGroups.response`` the answer).  One histogram of dictionary ids over the key columns
         (group-by..., aggregate key) per distinct aggregate key and one over (group-by...) for
@@ -1160,20 +1243,53 @@ class ColumnarIndex:
         one fused filter + histogram launch (``hip/group_agg.hip``), without them a
         ``np.bincount`` over the rows the CPU scan selected -- also for a histogram with more
         cells than the device takes.  The non-zero cells decode through the dictionaries into
-        ``AggGroups``; ``reduce_hist`` finishes, the same on every path."""
+        ``AggGroups``; ``reduce_hist`` finishes, the same on every path.
+        A key of ``extrema_keys`` whose histogram would pass ``EXTREMA_FROM_CELLS`` cells (a
+        timestamp: one dictionary value per write) gets no histogram unless ``hist`` asks for
+        it: one ``scan_extrema`` launch over the group columns and the key's rank-encoded copy
+        gives its count, smallest and largest rank per group, the row under each rank decodes
+        them -- O(groups).  Without kernels, or with more groups than the device takes,
+        ``extrema_numpy`` does the same over the CPU selection.  ``partial``: the answer in the
+        form shards merge (``AggGroups.response``)."""
         spec = parse_aggregate(q)
         # every referenced column first: one re-encode (source-backed) and one device upload
         self.ensure_columns(filter_paths(spec.filter) + spec.group_by + spec.keys)
         prog = self.compile_cached(spec.filter or {})
         gcols = [self.col_of[p] for p in spec.group_by]
+        gdims = [self._dict_size(c) for c in gcols]
+        gcells = math.prod(d + 1 for d in gdims)
+        cap = int(kernels.lib.tt_group_max_cells()) if kernels is not None else None
+        from_cells = self.EXTREMA_FROM_CELLS if cap is None else min(self.EXTREMA_FROM_CELLS, cap)
+        ext_keys = [] if hist else [k for k in extrema_keys(spec)
+                                    if gcells * (self._dict_size(self.col_of[k]) + 1) > from_cells]
+        ext_dev = kernels is not None and gcells <= cap  # else the groups alone are past the device
         dev = None
         if kernels is not None:
-            dev = (*self.mirror.program(prog, kernels), int(kernels.lib.tt_group_max_cells()))
+            dev = (*self.mirror.program(prog, kernels, [self.col_of[k] for k in ext_keys] if ext_dev else ()), cap)
         host_rows: list[np.ndarray] = []  # the CPU selection, made once when a histogram needs it
+
+        def selection() -> np.ndarray:
+            if not host_rows:
+                try:
+                    host_rows.append(self.select_native(prog))
+                except ImportError:
+                    host_rows.append(self.select_numpy(prog))
+            return host_rows[0]
+
+        def extrema(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+            """(cells, rows with a value, smallest, largest rank << 32 | row) of column ``kc``."""
+            if not ext_dev:
+                return self.extrema_numpy(selection(), gcols, gdims, kc)
+            m = dev[0]
+            cnt, lo, hi = kernels.scan_extrema(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims,
+                                               m.rank_slot[kc])
+            cnt = cnt.cpu().numpy().view(np.uint32)
+            cells = np.nonzero(cnt)[0]
+            return cells, cnt[cells], lo.cpu().numpy().view(np.uint64)[cells], hi.cpu().numpy().view(np.uint64)[cells]
 
         def histogram(cols: list[int]) -> tuple[np.ndarray, np.ndarray, list[int]]:
             """(non-zero cells, their counts, the axes' sizes) of the key columns ``cols``."""
-            dims = [len(self.columns[c].values) for c in cols]  # after the upload: widths match
+            dims = [self._dict_size(c) for c in cols]  # after the upload: widths match
             ncells = math.prod(d + 1 for d in dims)
             if ncells >= 1 << 62:
                 raise Unsupported("aggregate key space too large")
@@ -1182,11 +1298,7 @@ class ColumnarIndex:
                                             cols, dims).cpu().numpy().view(np.uint32)
                 cells = np.nonzero(counts)[0]
                 return cells, counts[cells], dims
-            if not host_rows:
-                try:
-                    host_rows.append(self.select_native(prog))
-                except ImportError:
-                    host_rows.append(self.select_numpy(prog))
+            selection()
             cell = np.zeros(host_rows[0].size, dtype=np.int64)
             for c, d in zip(cols, dims):
                 ids = self.ids[c, host_rows[0]]
@@ -1216,13 +1328,23 @@ class ColumnarIndex:
             groups.add_rows(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), n)
         for key in spec.keys:
             kc = self.col_of[key]
+            if key in ext_keys:
+                cells, counts, lo, hi = extrema(kc)
+                slots = decode(cells, gdims)
+                vals = self.columns[kc].values
+                lo_ids = self.ids[kc, (lo & np.uint64(0xFFFFFFFF)).astype(np.int64)].tolist()
+                hi_ids = self.ids[kc, (hi & np.uint64(0xFFFFFFFF)).astype(np.int64)].tolist()
+                for i, n in enumerate(counts.tolist()):
+                    groups.add_extrema(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), key, n,
+                                       vals[lo_ids[i]], vals[hi_ids[i]])
+                continue
             cells, counts, dims = histogram(gcols + [kc])
             slots = decode(cells, dims)
             for i, n in enumerate(counts.tolist()):
                 v = value(kc, slots[-1][i])
                 if v is not _MISSING:
                     groups.add_value(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), key, v, n)
-        return groups.response(hist)
+        return groups.response(hist, partial)
 
     # -- full query --------------------------------------------------------------
     def order(self, rows: np.ndarray, sort: list[dict[str, Any]] | None, k: int | None = None) -> np.ndarray:

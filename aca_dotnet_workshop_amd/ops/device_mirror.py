@@ -214,23 +214,28 @@ class DeviceMirror:
         cur.synced = ix.n
         return cur
 
-    def program(self, prog, kernels):
+    def program(self, prog, kernels, rank_cols=()):
         """Sync for ``prog`` and return (mirror, program, bitmaps) ready for ``GpuKernels.select``
-        (range leaves remapped to their rank-encoded columns)."""
+        (range leaves remapped to their rank-encoded columns).  ``rank_cols``: further columns to
+        keep rank-encoded copies of (``rank_slot`` has their rows of the table): the value
+        columns of ``GpuKernels.scan_extrema``."""
         leaf = (prog.code[:, 0] == OP_LEAF) | (prog.code[:, 0] == OP_EQ) | (prog.code[:, 0] == OP_RANGE)
         if leaf.any() and int(prog.code[leaf, 1].max()) >= len(self.index.columns):
             raise ValueError("program references a column outside the index")
+        if any(not 0 <= c < len(self.index.columns) for c in rank_cols):
+            raise ValueError("rank column outside the index")
         rng = prog.code[:, 0] == OP_RANGE
-        self.rank_cols = prog.code[rng, 1].tolist()
+        leaves = prog.code[rng, 1].tolist()
+        self.rank_cols = leaves + [int(c) for c in rank_cols]
         self.sync(kernels, self.rank_cols)
-        slots = tuple(sorted(self.rank_slot.items())) if rng.any() else ()
+        slots = tuple(sorted((c, self.rank_slot[c]) for c in set(leaves)))  # the program's own
         cached = prog.device
         if cached is not None and cached[0] == (slots, str(kernels.device)):
             return self, cached[1], cached[2]
         code_np = prog.code
         if rng.any():  # range leaves read the rank-encoded copy of their column
             code_np = prog.code.copy()
-            code_np[rng, 1] = [self.rank_slot[c] for c in self.rank_cols]
+            code_np[rng, 1] = [self.rank_slot[c] for c in leaves]
         code = kernels.torch.from_numpy(code_np).to(kernels.device)
         bitmaps = kernels.torch.from_numpy(prog.bitmaps).to(kernels.device)
         prog.device = ((slots, str(kernels.device)), code, bitmaps)  # reused while the slots hold

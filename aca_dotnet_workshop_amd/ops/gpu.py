@@ -51,6 +51,9 @@ def load_library(build: bool = True) -> ctypes.CDLL:
     lib.tt_launch_scan_group.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, P, I32, P]
     lib.tt_launch_scan_group.restype = ctypes.c_int
     lib.tt_group_max_cells.restype = ctypes.c_int
+    lib.tt_launch_scan_extrema.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, P, P, I32, P]
+    lib.tt_launch_scan_extrema.restype = ctypes.c_int
+    lib.tt_extrema_max_lds_cells.restype = ctypes.c_int
     lib.tt_launch_sort_keys.argtypes = [P, P, I64, P, I32, P, I32, P, I32, P, P, I32, P]
     lib.tt_launch_sort_keys.restype = ctypes.c_int
     lib.tt_sort_max_keys.restype = ctypes.c_int
@@ -390,6 +393,54 @@ class GpuKernels:
         if rc != 0:
             raise RuntimeError(f"tt_scan_group launch failed ({rc})")
         return counts
+
+    extrema_scans = 0  # tt_scan_extrema launches
+
+    def scan_extrema(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, value_col: int,
+                     max_blocks: int = 0, out=None):
+        """Per group cell, over the live rows satisfying ``prog`` whose value is defined: (counts
+        int32 holding uint32, lo int64, hi int64 holding uint64), ``lo`` / ``hi`` the smallest and
+        the largest ``code << 32 | row`` of the value column -- filter and reduction in one pass
+        (``hip/group_extrema.hip`` tt_scan_extrema).  ``keys`` / ``dims``: up to 2 group columns
+        and their dictionary sizes, cells as for ``scan_group``; ``value_col``: the row of
+        ``table`` whose codes are compared as unsigned integers (a rank-encoded copy), its
+        all-ones code = undefined.  ``lo`` / ``hi`` of a cell mean something only where its count
+        is not 0.  ``out``: a (counts, lo, hi) triple initialised to 0 / -1 / 0 to reduce into
+        instead of a new one.  ValueError when the cells exceed ``tt_group_max_cells()``."""
+        torch = self.torch
+        keys, dims, value_col = [int(x) for x in keys], [int(x) for x in dims], int(value_col)
+        if len(keys) != len(dims) or len(keys) > 2:
+            raise ValueError("at most 2 group columns, one dictionary size each")
+        self._check_scan_args(table, live16, capacity, nrows, prog)
+        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
+            raise ValueError("group columns must be rows of the column table, dictionary sizes >= 0")
+        if not 0 <= value_col < table.shape[0]:
+            raise ValueError("the value column must be a row of the column table")
+        if nrows > 1 << 32:
+            raise ValueError("rows past 2^32 do not fit next to the code")
+        ncells = 1
+        for d in dims:
+            ncells *= d + 1
+        limit = int(self.lib.tt_group_max_cells())
+        n = min(ncells, limit)
+        if out is None:
+            out = (torch.zeros(n, dtype=torch.int32, device=self.device),
+                   torch.full((n,), -1, dtype=torch.int64, device=self.device),
+                   torch.zeros(n, dtype=torch.int64, device=self.device))
+        elif len(out) != 3 or out[0].dtype != torch.int32 or out[1].dtype != torch.int64 or \
+                out[2].dtype != torch.int64 or any(t.numel() < n for t in out):
+            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
+        rc = self.lib.tt_launch_scan_extrema(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
+                                             prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
+                                             (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims), len(keys),
+                                             value_col, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                             max_blocks, self._stream())
+        if rc == -2:
+            raise ValueError(f"{ncells} group cells exceed the device limit of {limit}")
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_extrema launch failed ({rc})")
+        self.extrema_scans += 1
+        return out
 
     def sort_keys(self, table, rows, specs, ranks, seq, seq_bits: int, hist=None, shift: int = 0):
         """Packed 63-bit ordering keys (int64) for ``rows`` (int32, device): see
