@@ -14,6 +14,7 @@ functions over ``GpuKernels`` and read the buffers back.
 """
 import ctypes
 import json
+import math
 import random
 from types import SimpleNamespace
 
@@ -23,7 +24,8 @@ import pytest
 from aca_dotnet_workshop_amd import native
 from aca_dotnet_workshop_amd.ops.codes import OP_RANGE, encode_codes, gather, width_for
 from aca_dotnet_workshop_amd.ops.columnar import ColumnarIndex, Program
-from test_gpu_kernel_edges import MISSING, TILE, _live16, _pack, ref_keys, ref_page, ref_select
+from test_gpu_group_extrema import ref_extrema
+from test_gpu_kernel_edges import MISSING, TILE, _Synth, _live16, _pack, ref_keys, ref_page, ref_select
 
 _CODE_DT = {1: np.uint8, 2: np.uint16, 4: np.int32}
 
@@ -89,12 +91,14 @@ class HostKernels:
     width, the liveness words, the sequence -- with the references of ``test_gpu_kernel_edges``;
     never from the index.  A buffer the mirror failed to bring up to date gives a wrong answer."""
 
-    def __init__(self, cap=TILE):
+    def __init__(self, cap=TILE, max_cells=1 << 22):
         self.torch = _CopyingTorch()
         self.device = self.torch.device("cpu")
         self.page_cap, self.max_sort_keys = cap, 4
-        self.lib = SimpleNamespace(tt_group_max_cells=lambda: 1 << 22)
+        self.max_cells = max_cells  # the device's is 2^22: a smaller one puts the fallbacks in reach
+        self.lib = SimpleNamespace(tt_group_max_cells=lambda: self.max_cells)
         self.calls = {"zone_tiles": 0, "page_tiles": 0, "pages": 0, "rank_rows": 0}
+        self.extrema_scans = 0  # as GpuKernels counts them
         self.uploads = 0  # scatters that carried bytes, as GpuKernels counts them
 
     # -- writes
@@ -181,7 +185,42 @@ class HostKernels:
             keep &= ids < d  # ids at or past the dictionary size are dropped
             cell = cell * (d + 1) + np.where(ids < 0, d, ids)
             ncells *= d + 1
+        if ncells > self.max_cells:
+            raise ValueError(f"{ncells} histogram cells exceed the device limit of {self.max_cells}")
         return torch.from_numpy(np.bincount(cell[keep], minlength=ncells).astype(np.uint32).view(np.int32))
+
+    def scan_extrema(self, table, live16, capacity, nrows, prog, bitmaps, keys, dims, value_col, max_blocks=0,
+                     out=None):
+        """``GpuKernels.scan_extrema`` by ``ref_extrema`` (the function the GPU suite compares
+        with the kernel word for word) over the columns decoded from the descriptor table: the
+        group columns and the value column are rows of ``table``, nothing else is known here."""
+        import torch
+        keys, dims, value_col = [int(x) for x in keys], [int(x) for x in dims], int(value_col)
+        if len(keys) != len(dims) or len(keys) > 2:
+            raise ValueError("at most 2 group columns, one dictionary size each")
+        if capacity % TILE or not 0 <= nrows <= capacity or live16.numel() * 16 < capacity:
+            raise ValueError("rows, capacity and liveness words do not agree")
+        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
+            raise ValueError("group columns must be rows of the column table, dictionary sizes >= 0")
+        if not 0 <= value_col < table.shape[0]:
+            raise ValueError("the value column must be a row of the column table")
+        ncells = math.prod(d + 1 for d in dims)
+        if ncells > self.max_cells:
+            raise ValueError(f"{ncells} group cells exceed the device limit of {self.max_cells}")
+        if out is None:
+            out = (torch.zeros(ncells, dtype=torch.int32), torch.full((ncells,), -1, dtype=torch.int64),
+                   torch.zeros(ncells, dtype=torch.int64))
+        elif len(out) != 3 or out[0].dtype != torch.int32 or out[1].dtype != torch.int64 or \
+                out[2].dtype != torch.int64 or any(t.numel() < ncells for t in out):
+            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
+        T = SimpleNamespace(cols=self._cols(table, nrows), live=self._live(live16, nrows), n=nrows)
+        (cnt, lo, hi), *_ = ref_extrema(T, prog.numpy(), bitmaps.numpy(), keys, dims, value_col)
+        c, l, h = out[0].numpy().view(np.uint32), out[1].numpy().view(np.uint64), out[2].numpy().view(np.uint64)
+        c[:ncells] += cnt
+        l[:ncells] = np.minimum(l[:ncells], lo)
+        h[:ncells] = np.maximum(h[:ncells], hi)
+        self.extrema_scans += 1
+        return out
 
     def sort_keys(self, table, rows, specs, ranks, seq, seq_bits, hist=None, shift=0):
         import torch
@@ -877,3 +916,82 @@ def test_stand_in_grouped_and_ordered_queries_match_the_host():
             qq = {"filter": F_PAGE, "page": page, **({"sort": sort} if sort else {})}
             assert ix.query(qq, kernels) == ix.query(qq)
         run.order(F_PAGE, sort)
+
+
+def test_stand_in_extrema_over_a_hand_packed_table_match_extrema_numpy():
+    """``HostKernels.scan_extrema`` over a table packed here by ``_pack`` -- the index's ids and, as
+    the value column, the ranks of a column whose values arrive in no order -- equals
+    ``ColumnarIndex.extrema_numpy`` over the same rows; two launches into one ``out`` triple
+    merge to the launch over both halves; what ``GpuKernels.scan_extrema`` refuses is refused."""
+    import torch
+    rnd = random.Random(9)
+    ix = ColumnarIndex(PATHS, capacity=2 * TILE)
+    for i in range(TILE + 41):
+        ix.upsert(f"k{i}", _doc(rnd, stamps=3000))
+    for i in rnd.sample(range(TILE + 41), 400):
+        ix.delete(f"k{i}")
+    n, cap = ix.n, ix.cap
+    b, m, c = ix.col_of["b"], ix.col_of["m"], ix.col_of["c"]
+    ranks = ix.columns[c].ranks()
+    assert (np.diff(ranks) < 0).any()  # ids do not order like ranks
+    widths = [width_for(len(col.values)) for col in ix.columns]
+    assert widths[b] == 0 and widths[m] == 1 and widths[c] == 2
+    cols = [(ix.ids[i, :n].copy(), w) for i, w in enumerate(widths)]
+    slot = len(cols)
+    cols.append((gather(ranks, ix.ids[c, :n], -1).astype(np.int32), 2))
+    kernels = HostKernels(max_cells=200)
+    T = _Synth(kernels, cols, ix.live[:n] != 0, n, cap)
+    prog = ix.compile({"EQ": {"b": False}})
+    assert not (prog.code[:, 0] == OP_RANGE).any()
+    code, bitmaps = torch.from_numpy(prog.code), torch.from_numpy(prog.bitmaps)
+    true = ix.compile({})
+    everything = (torch.from_numpy(true.code), torch.from_numpy(true.bitmaps))
+
+    def device(keys, dims, program=(code, bitmaps), live16=T.live16, out=None):
+        got = kernels.scan_extrema(T.table, live16, cap, n, *program, keys, dims, slot, out=out)
+        assert out is None or got is out
+        cnt = got[0].numpy().view(np.uint32)
+        cells = np.nonzero(cnt)[0]
+        return [cells, cnt[cells], got[1].numpy().view(np.uint64)[cells], got[2].numpy().view(np.uint64)[cells]]
+
+    def same(got, want):
+        return all(np.array_equal(g, np.asarray(w).astype(g.dtype)) for g, w in zip(got, want))
+
+    rows = ix.select_numpy(prog)
+    assert 1000 < rows.size < n
+    for keys in ([], [b], [m], [m, b]):
+        dims = [len(ix.columns[k].values) for k in keys]
+        before = kernels.extrema_scans
+        got = device(keys, dims)
+        assert kernels.extrema_scans == before + 1
+        want = ix.extrema_numpy(rows, keys, dims, c)
+        assert same(got, want) and want[0].size >= 1, keys
+        # lo / hi: rank << 32 | row, and the row holds that rank
+        assert np.array_equal(ranks[ix.ids[c, (got[2] & np.uint64(0xFFFFFFFF)).astype(np.int64)]],
+                              (got[2] >> np.uint64(32)).astype(np.int64))
+    # ``out=``: the rows of the even and of the odd tiles' worth of liveness words, one triple
+    alive = ix.live[:n] != 0
+    halves = [alive & (np.arange(n) % 32 < 16), alive & (np.arange(n) % 32 >= 16)]
+    dims = [len(ix.columns[m].values)]
+    out = (torch.zeros(dims[0] + 1, dtype=torch.int32), torch.full((dims[0] + 1,), -1, dtype=torch.int64),
+           torch.zeros(dims[0] + 1, dtype=torch.int64))
+    for half in halves:
+        merged = device([m], dims, everything, torch.from_numpy(_live16(half, cap).copy()), out)
+    assert same(merged, ix.extrema_numpy(np.nonzero(alive)[0].astype(np.int32), [m], dims, c))
+    assert not same(merged, ix.extrema_numpy(np.nonzero(halves[1])[0].astype(np.int32), [m], dims, c))
+    # refusals, as GpuKernels.scan_extrema's
+    ncols = len(cols)
+    before = kernels.extrema_scans
+    for keys, dims, vcol in (([b, m, b], [3, 40, 3], slot), ([b], [3, 4], slot), ([ncols], [3], slot), ([-1], [3], slot),
+                             ([b], [-1], slot), ([b], [3], ncols), ([b], [3], -1),
+                             ([m, b], [50, 3], slot), ([m], [200], slot)):  # 204 and 201 cells: past the 200 allowed
+        with pytest.raises(ValueError):
+            kernels.scan_extrema(T.table, T.live16, cap, n, code, bitmaps, keys, dims, vcol)
+    kernels.scan_extrema(T.table, T.live16, cap, n, code, bitmaps, [m], [199], slot)  # exactly 200 cells
+    for bad in (out[:2], (out[1], out[1], out[2]), (out[0], out[1][:10], out[2])):
+        with pytest.raises(ValueError):
+            kernels.scan_extrema(T.table, T.live16, cap, n, code, bitmaps, [m], [40], slot, out=bad)
+    assert kernels.extrema_scans == before + 1
+    with pytest.raises(ValueError):  # the histogram's cap is the same one
+        kernels.scan_group(T.table, T.live16, cap, n, code, bitmaps, [m, b], [50, 3])
+    assert int(kernels.scan_group(T.table, T.live16, cap, n, code, bitmaps, [m, b], [49, 3]).sum()) == rows.size
