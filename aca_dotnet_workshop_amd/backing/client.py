@@ -128,7 +128,9 @@ class BackingClient:
         """Grouped aggregates (``{"filter", "groupBy", "aggregate"}`` -> ``{"groups": [...]}``);
         ``hist``: the raw histograms per aggregate key instead of the reduced values;
         ``partial``: the form a merge of several stores needs at the least size -- [count, min,
-        max] for the keys of which no more is asked, histograms for the others."""
+        max] for the keys of which no more is asked, exact scaled-integer sums ``[nums, S, A, e]``
+        for a SUM / AVG key with too many distinct numbers for a histogram, histograms for the
+        others."""
         project = "hist" if hist else "partial" if partial else ""
         args = {**({"prefix": prefix} if prefix else {}), **({"project": project} if project else {})}
         path = f"{self._coll(account, db, coll)}/aggregate" + ("?" + urlencode(args) if args else "")

@@ -208,7 +208,8 @@ class BackingServices:
         a TTL collection, a filter the mirror does not take -- over the documents the native
         engine's query returns, reduced by the same ``AggGroups`` / ``reduce_hist``.  ``hist``:
         the raw histograms; ``partial``: [count, min, max] for the keys of which no more is asked,
-        histograms for the others (either is a shard's share of a partitioned collection).
+        exact scaled-integer sums for a high-cardinality SUM / AVG key (``AggGroups``), histograms
+        for the others (either is a shard's share of a partitioned collection).
         Returns (200, result JSON) -- the result-size RU are debited here -- or (400, the error).
         Blocking."""
         s = self.store(account, db, coll)
@@ -405,7 +406,8 @@ class BackingServices:
             # ?project=hist: per group the raw (value, rows) histogram of each aggregate key --
             # a shard's share, which the partitioned client adds up before reducing once
             # ?project=partial: the same with [count, min, max] in place of the histogram of a key
-            # of which only COUNT / MIN / MAX are asked (a timestamp's histogram is the column)
+            # of which only COUNT / MIN / MAX are asked (a timestamp's histogram is the column), and
+            # "sum": [nums, S, A, e] for a SUM / AVG key with about one distinct number per row
             project = (req.query_get("project", "") or "").lower()
             hist = project == "hist"
             if (t := throttled(req, s, s.query_ru(0), 2)) is not None:

@@ -281,22 +281,31 @@ class ShardedBackingClient:
 
     async def doc_aggregate(self, account, db, coll, query: bytes, prefix: str = "", hist: bool = False,
                             partial: bool = False) -> bytes:
-        """Every shard's partial answer -- raw histograms, and [count, min, max] for the keys of
-        which no more is asked (``project=partial``; with ``hist`` histograms throughout) -- the
-        counts of equal groups and values added, the extrema merged, reduced once: the answer of
-        one store over the same documents (an average of averages or a sum of rounded sums
-        would not be)."""
-        from ..ops.columnar import AggGroups, parse_aggregate
+        """Every shard's partial answer -- raw histograms, [count, min, max] for the keys of
+        which no more is asked and exact scaled-integer sums for high-cardinality SUM / AVG keys
+        (``project=partial``; with ``hist`` histograms throughout) -- the counts of equal groups
+        and values added, the extrema and the sums merged, reduced once: the answer of one store
+        over the same documents (an average of averages or a sum of rounded sums would not be).
+        Merged sums that no longer prove their SUM (``Inexact``: magnitudes past 2^53) send the
+        request round again for histograms."""
+        from ..ops.columnar import AggGroups, Inexact, parse_aggregate
         try:
             spec = parse_aggregate(json.loads(query or b"{}"))
         except ValueError as ex:
             raise BackingError(400, str(ex).encode(), "state aggregate") from None
-        parts = await asyncio.gather(*(c.doc_aggregate(account, db, coll, query, prefix, hist=hist, partial=not hist)
-                                       for c in self.shards))
-        groups = AggGroups(spec)
-        for body in parts:
-            groups.add_response(json.loads(body))
-        return json.dumps(groups.response(hist, partial), separators=(",", ":")).encode()
+
+        async def merged(as_hist: bool) -> "AggGroups":
+            parts = await asyncio.gather(*(c.doc_aggregate(account, db, coll, query, prefix, hist=as_hist,
+                                                           partial=not as_hist) for c in self.shards))
+            groups = AggGroups(spec)
+            for body in parts:
+                groups.add_response(json.loads(body))
+            return groups
+        try:
+            res = (await merged(hist)).response(hist, partial)
+        except Inexact:
+            res = (await merged(True)).response(hist, partial)
+        return json.dumps(res, separators=(",", ":")).encode()
 
     async def doc_stats(self, account, db, coll):
         parts = await asyncio.gather(*(c.doc_stats(account, db, coll) for c in self.shards))

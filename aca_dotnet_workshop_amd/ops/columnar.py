@@ -229,13 +229,42 @@ def extrema_keys(spec: AggSpec) -> list[str]:
     return [k for k in spec.keys if all(op in EXTREMA_OPS for op, kk in spec.aggs if kk == k)]
 
 
+def sum_keys(spec: AggSpec) -> list[str]:
+    """The aggregate keys that are asked a SUM or an AVG: exact scaled-integer sums per group can
+    answer those (``AggGroups.add_sums``), their COUNT / MIN / MAX then come from extrema."""
+    return [k for k in spec.keys if any(op in ("SUM", "AVG") for op, kk in spec.aggs if kk == k)]
+
+
+class Inexact(Exception):
+    """A group's scaled-integer sums cannot prove its SUM (``AggGroups``): the sum of magnitudes
+    reached 2^53.  The histograms answer (``hist=True``); not a malformed request."""
+
+
+def _scaled(v: Any) -> tuple[int, int] | None:
+    """(m, e), ``float(v) == m * 2^e`` exactly with e <= 0; None for a number that is not finite."""
+    try:
+        num, den = float(v).as_integer_ratio()
+    except (OverflowError, ValueError):
+        return None
+    return num, 1 - den.bit_length()
+
+
 class AggGroups:
     """Per group (the group-by values, a missing path apart from JSON null): its row count and,
     per aggregate key, the histogram of the key's values -- or, for a key of ``extrema_keys``,
     its extrema: [rows where it is defined, smallest value, largest value].  Counts of equal
     groups and values (``vkey``) add and extrema merge by ``compare``, so partial answers --
     launches, shards -- merge by adding themselves.  Which form a key is held in follows from
-    the request and the path taken, the same for every part of one answer."""
+    the request and the path taken, the same for every part of one answer.
+
+    A key of ``sum_keys`` may also be held as sums of scaled integers, ``[nums, S, A, e]``: over
+    the ``nums`` rows whose value is a number ``m * 2^e``, S = the sum of the m and A = the sum
+    of the |m| (Python ints), with extrema next to them when COUNT / MIN / MAX are asked too.
+    While A < 2^53 every product value x rows is exact in a double and so is their sum:
+    ``reduce_hist``'s correctly rounded SUM is ``ldexp(S, e)``.  Such sums merge with one another
+    (rescaled to the smaller e) and with histograms of the same key from parts below the
+    threshold, whose numeric pairs are folded in exactly; at A >= 2^53 the reduction raises
+    ``Inexact`` and the caller asks for histograms."""
 
     def __init__(self, spec: AggSpec) -> None:
         self.spec = spec
@@ -248,8 +277,40 @@ class AggGroups:
         g = self.groups.get(gk)
         if g is None:
             g = self.groups[gk] = {"values": tuple(v if v is _MISSING else _canon(v) for v in gvals), "count": 0,
-                                   "hist": {k: {} for k in self.spec.keys}, "ext": {}}
+                                   "hist": {k: {} for k in self.spec.keys}, "ext": {}, "sum": {}}
         return g
+
+    def add_sums(self, gvals: tuple, key: str, nums: int, s: int = 0, a: int = 0, e: int = 0) -> None:
+        """``nums`` rows of the group hold a number under ``key``, ``s`` and ``a`` the sums of
+        their m and |m| at the quantum 2^``e``; nothing when ``nums`` is 0."""
+        if not nums:
+            return
+        sums = self._group(gvals)["sum"]
+        cur = sums.get(key)
+        sums[key] = [int(nums), int(s), int(a), int(e)] if cur is None else \
+            self._merged(cur, [int(nums), int(s), int(a), int(e)])
+
+    @staticmethod
+    def _merged(x: list, y: list) -> list:
+        e = min(x[3], y[3])
+        return [x[0] + y[0], (x[1] << (x[3] - e)) + (y[1] << (y[3] - e)),
+                (x[2] << (x[3] - e)) + (y[2] << (y[3] - e)), e]
+
+    def _sums(self, g: dict[str, Any], key: str) -> list | None:
+        """[nums, S, A, e] of ``key`` in group ``g``: its sums with the numeric pairs of its
+        histogram folded in ([0, 0, 0, 0] without a number); None when a pair is not finite.
+        e only ever falls: 2^e divides every single m that went in, which is what A < 2^53
+        speaks about -- a coarser spelling of the same S and A (their common trailing zeros
+        shifted out) would hide a product that rounds, so the same content may arrive at
+        different e from different paths (a column's scale, a group's own)."""
+        out = g["sum"].get(key) or [0, 0, 0, 0]
+        for v, c in g["hist"][key].values():
+            if c and type_rank(v) == 2:
+                me = _scaled(v)
+                if me is None:
+                    return None
+                out = self._merged(out, [c, me[0] * c, abs(me[0]) * c, me[1]])
+        return list(out)
 
     def add_extrema(self, gvals: tuple, key: str, count: int, lo_value: Any = None, hi_value: Any = None) -> None:
         """``count`` rows of the group hold ``key``, their values between ``lo_value`` and
@@ -298,23 +359,70 @@ class AggGroups:
                     self.add_value(gvals, k, v, c)
             for k, e in g.get("ext", {}).items():
                 self.add_extrema(gvals, k, *e)
+            for k, e in g.get("sum", {}).items():
+                self.add_sums(gvals, k, *e)
 
     def _extrema(self, g: dict[str, Any], key: str) -> list | None:
-        """[count, min, max] of ``key`` in group ``g`` from its extrema when it holds them, else
-        from its histogram; None without a defined value."""
+        """[count, min, max] of ``key`` in group ``g`` from its extrema and its histogram (a key
+        held as sums may have both, from different parts); None without a defined value."""
         e = g["ext"].get(key)
-        if e is not None:
-            return e
         r = reduce_hist(g["hist"][key].values(), ("COUNT", "MIN", "MAX"))
-        return [r["COUNT"], r["MIN"], r["MAX"]] if r["COUNT"] else None
+        if not r["COUNT"]:
+            return e
+        if e is None:
+            return [r["COUNT"], r["MIN"], r["MAX"]]
+        return [e[0] + r["COUNT"], r["MIN"] if compare(r["MIN"], e[1]) < 0 else e[1],
+                r["MAX"] if compare(r["MAX"], e[2]) > 0 else e[2]]
+
+    def _reduce_forms(self, g: dict[str, Any], key: str, ops: list[str]) -> dict[str, Any]:
+        """``reduce_hist`` for a key that group ``g`` holds as extrema or sums (and maybe a
+        histogram next to them).  ``Inexact`` when the sums do not prove the SUM."""
+        out: dict[str, Any] = {}
+        x = self._extrema(g, key)
+        if "COUNT" in ops:
+            out["COUNT"] = x[0] if x else 0
+        if x:
+            out.update((op, v) for op, v in (("MIN", x[1]), ("MAX", x[2])) if op in ops)
+        if key not in g["sum"]:
+            out.update(reduce_hist(g["hist"][key].values(), [op for op in ops if op in ("SUM", "AVG")]))
+            return out
+        t = self._sums(g, key)
+        if t is None or t[2] >= 1 << 53:
+            raise Inexact(f"sum of magnitudes of {key!r} past 2^53")
+        s = math.ldexp(float(t[1]), t[3])
+        out.update((op, v) for op, v in (("SUM", s), ("AVG", (s, t[0]))) if op in ops)
+        return out
+
+    def _sum_form(self) -> dict[str, dict]:
+        """The keys a partial answer carries as sums, each with its folded sums per group (by
+        ``id``): a key of ``sum_keys`` that some group holds as sums already, or whose histograms
+        have more pairs than ``ColumnarIndex.SUMS_FROM_CELLS`` (a document walk over a
+        high-cardinality key) and prove every group's SUM here (magnitudes below 2^53: not 0.1
+        next to 1e16, which stays a histogram)."""
+        out = {}
+        for k in sum_keys(self.spec):
+            gs = list(self.groups.values())
+            held = any(k in g["sum"] for g in gs)
+            if not held and sum(len(g["hist"][k]) for g in gs) <= ColumnarIndex.SUMS_FROM_CELLS:
+                continue
+            folded = {id(g): self._sums(g, k) for g in gs}
+            if held and any(t is None for t in folded.values()):
+                raise Inexact(f"a number of {k!r} next to its sums is not finite")
+            if all(t is not None and (held or t[2] < 1 << 53) for t in folded.values()):
+                out[k] = folded
+        return out
 
     def response(self, hist: bool = False, partial: bool = False) -> dict[str, Any]:
         """The route's answer: groups sorted by their values (``compare``, a missing path
         first); ``hist``: the raw histograms per aggregate key instead of the reduced values;
         ``partial`` (without ``hist``): what another ``AggGroups`` merges (``add_response``)
         at the least size -- ``"ext": {key: [count, min, max]}`` for the keys of
-        ``extrema_keys`` (``[0]``: no defined value) and ``"hist"`` for the others."""
+        ``extrema_keys`` (``[0]``: no defined value), ``"sum": {key: [nums, S, A, e]}`` (``[0]``:
+        no number; present only when some key is in that form, see ``_sum_form``) with ``"ext"``
+        for the COUNT / MIN / MAX asked of the same key, and ``"hist"`` for the others."""
         ext_keys = set() if hist else set(extrema_keys(self.spec))
+        sum_form = self._sum_form() if partial and not hist else {}
+        sum_ext = {k for k in sum_form if any(op in EXTREMA_OPS for op, kk in self.spec.aggs if kk == k)}
         def cmp(a: dict, b: dict) -> int:
             for x, y in zip(a["values"], b["values"]):
                 if x is _MISSING or y is _MISSING:
@@ -333,15 +441,17 @@ class AggGroups:
             if hist or partial:
                 o["hist"] = {k: sorted(([v, c] for v, c in h.values()),
                                        key=functools.cmp_to_key(lambda a, b: compare(a[0], b[0])))
-                             for k, h in g["hist"].items() if k not in ext_keys}
+                             for k, h in g["hist"].items() if k not in ext_keys and k not in sum_form}
                 if not hist:
-                    o["ext"] = {k: self._extrema(g, k) or [0] for k in self.spec.keys if k in ext_keys}
+                    o["ext"] = {k: self._extrema(g, k) or [0] for k in self.spec.keys if k in ext_keys or k in sum_ext}
+                    if sum_form:
+                        o["sum"] = {k: t[id(g)] if t[id(g)][0] else [0] for k, t in sum_form.items()}
             else:
                 red = {}
                 for k, h in g["hist"].items():
                     ops = [op for op, kk in self.spec.aggs if kk == k]
-                    if k in g["ext"]:
-                        red[k] = {op: v for op, v in zip(("COUNT", "MIN", "MAX"), g["ext"][k]) if op in ops}
+                    if k in g["ext"] or k in g["sum"]:
+                        red[k] = self._reduce_forms(g, k, ops)
                     else:
                         red[k] = reduce_hist(h.values(), ops)
                 aggs = []
@@ -424,6 +534,17 @@ def _native_module():
     return _NATIVE[0]
 
 
+NOT_A_NUMBER = -1 << 63  # in a table of scaled integers (``Column.nums``): the value is no number
+
+
+def _quanta(f: np.ndarray) -> np.ndarray:
+    """Per finite double the exponent q of its lowest set bit, ``f == odd * 2^q`` (0 for 0.0)."""
+    mant, exp = np.frexp(f)
+    m53 = np.ldexp(mant, 53).astype(np.int64)  # the 53-bit significand as an integer: exact
+    low = (m53 & -m53).astype(np.float64)      # its lowest set bit, a power of two
+    return np.where(m53 == 0, 0, exp.astype(np.int64) - 53 + np.frexp(low)[1] - 1)
+
+
 class Column:
     def __init__(self, path: str) -> None:
         self.path = path
@@ -445,6 +566,15 @@ class Column:
         self._str_sorted = None
         self._nr = None       # native/src/strrank.hpp StrRanker (the string-only ranks)
         self._nr_buf = None   # its rank buffer (int64, capacity-doubled, owned here)
+        # the number scale (``num_scale``): values[:_scale_n] are in it; float(v) = m * 2^e with
+        # ``_scale_m[id]`` = m as a Python-exact int64 (NOT_A_NUMBER for a value that is no number)
+        self._scale_n = 0
+        self._scale_e = 0
+        self._scale_max = 0          # max |m|
+        self._scale_any = False      # the dictionary holds a number
+        self._scale_bad = False      # ... one that is not finite, or whose m leaves int64
+        self._scale_m = np.zeros(0, dtype=np.int64)  # capacity-doubled
+        self.scale_epoch = 0         # bumps when every m changed (e dropped, dictionary replaced)
 
     @property
     def ids(self) -> dict[str, int]:
@@ -526,6 +656,71 @@ class Column:
             c = compare(x, val)
             out[i] = {"GT": c > 0, "GTE": c >= 0, "LT": c < 0, "LTE": c <= 0}[op]
         return out
+
+    def num_scale(self, rows: int = 1) -> tuple[int, int] | None:
+        """(e, max |m|): the largest power-of-two quantum 2^e, -1074 <= e <= 0, of which every
+        number of the dictionary (``type_rank`` 2: int and float, not bool) is an integer
+        multiple, ``float(v) == m * 2^e`` -- integers have e = 0, 2.5 makes it -1, 0.1 makes it
+        -55 -- and the largest magnitude among the m.  ``m`` is that of ``float(v)``: an int past
+        2^53 counts as its double, as ``reduce_hist`` adds it.  None when the dictionary holds no
+        number, one that is not finite, or when ``max|m| * max(rows, 1)`` reaches 2^63: ``rows``
+        scaled integers could then wrap a 64-bit sum.  Kept incrementally: new dictionary values
+        extend the table of m (``nums``), one that lowers e rescales it (``scale_epoch`` bumps)."""
+        self._scale_extend()
+        if self._scale_bad or not self._scale_any or self._scale_max * max(int(rows), 1) >= 1 << 63:
+            return None
+        return self._scale_e, self._scale_max
+
+    def nums(self, lo: int, hi: int) -> np.ndarray:
+        """The m of ids [lo, hi) at the scale of ``num_scale`` (int64; ``NOT_A_NUMBER`` for a value
+        that is no number).  Only while ``num_scale()`` is not None."""
+        self._scale_extend()
+        return self._scale_m[lo:hi]
+
+    def _scale_extend(self) -> None:
+        n = len(self.values)
+        if self._scale_n > n:  # the dictionary was replaced
+            self._scale_n, self._scale_e, self._scale_max = 0, 0, 0
+            self._scale_any = self._scale_bad = False
+            self.scale_epoch += 1
+        if self._scale_n == n:
+            return
+        lo, self._scale_n = self._scale_n, n
+        if self._scale_bad:
+            return
+        new = self.values[lo:n]
+        isnum = np.fromiter((type_rank(v) == 2 for v in new), dtype=bool, count=len(new))
+        if self._scale_m.size < n:
+            grown = np.empty(max(1024, 2 * n), dtype=np.int64)
+            grown[:lo] = self._scale_m[:lo]
+            self._scale_m = grown
+        self._scale_m[lo:n] = NOT_A_NUMBER
+        if not isnum.any():
+            return
+        try:
+            f = np.array([float(v) for v, k in zip(new, isnum) if k], dtype=np.float64)
+        except OverflowError:  # an int past the doubles
+            f = np.array([np.inf])
+        if not np.isfinite(f).all():
+            self._scale_bad, self._scale_m = True, np.zeros(0, dtype=np.int64)
+            return
+        e = min(self._scale_e, int(_quanta(f).min()))
+        if e < self._scale_e:  # every m so far is rescaled to the finer quantum
+            shift = self._scale_e - e
+            self._scale_max <<= shift
+            if 0 < self._scale_max < 1 << 63:  # (all zeros: nothing to shift)
+                old = self._scale_m[:lo]
+                np.left_shift(old, shift, out=old, where=old != NOT_A_NUMBER)
+            self._scale_e = e
+            self.scale_epoch += 1
+        with np.errstate(over="ignore"):
+            m = np.ldexp(f, -e)  # integers: exact unless past the doubles (inf)
+        self._scale_max = max(self._scale_max, int(np.abs(m).max()) if np.isfinite(m).all() else 1 << 63)
+        if self._scale_max >= 1 << 63:
+            self._scale_bad, self._scale_m = True, np.zeros(0, dtype=np.int64)
+            return
+        self._scale_any = True
+        self._scale_m[lo:n][isnum] = m.astype(np.int64)
 
     def missing_rank(self) -> int:
         """A missing path sorts like JSON null (the native engine compares it as null)."""
@@ -1210,6 +1405,36 @@ class ColumnarIndex:
     # have more cells than this; with kernels, than the smaller of this and the device's cap.
     EXTREMA_FROM_CELLS = 1 << 22
 
+    # An aggregate key that is asked a SUM or an AVG leaves the histogram for exact scaled-integer
+    # sums per group (``hip/group_sums.hip``, ``sums_numpy``) when its histogram would have more
+    # cells than this and its numbers share a scale (``Column.num_scale``).  Compared alone, not
+    # with the device's cap (in production the two are equal).
+    SUMS_FROM_CELLS = 1 << 22
+
+    def sums_numpy(self, rows: np.ndarray, gcols: list[int], gdims: list[int],
+                   kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Host twin of ``hip/group_sums.hip`` over the selected ``rows``: (cells with a number
+        in column ``kc``, how many rows hold one, the sum of their scaled integers m as int64, the
+        sum of |m| as uint64), the cell of a row as in ``aggregate``'s histograms of the group
+        columns.  Integer adds only (``reduceat``): exact, whatever the order."""
+        col = self.columns[kc]
+        ids = self.ids[kc, rows]
+        rows, ids = rows[ids >= 0], ids[ids >= 0]
+        m = col.nums(0, len(col.values))[ids] if ids.size else np.zeros(0, dtype=np.int64)
+        rows, m = rows[m != NOT_A_NUMBER], m[m != NOT_A_NUMBER]
+        cell = np.zeros(rows.size, dtype=np.int64)
+        for c, d in zip(gcols, gdims):
+            g = self.ids[c, rows]
+            cell = cell * (d + 1) + np.where(g < 0, d, g)
+        if not cell.size:
+            return cell, cell, m, m.astype(np.uint64)
+        order = np.argsort(cell, kind="stable")
+        cell, m = cell[order], m[order]
+        starts = np.flatnonzero(np.concatenate([[True], cell[1:] != cell[:-1]]))
+        ends = np.concatenate([starts[1:], [cell.size]])
+        return (cell[starts], ends - starts, np.add.reduceat(m, starts),
+                np.add.reduceat(np.abs(m).astype(np.uint64), starts))
+
     def _dict_size(self, col: int) -> int:
         """The dictionary size of a column as the aggregate planner sees it."""
         return len(self.columns[col].values)
@@ -1249,8 +1474,15 @@ class ColumnarIndex:
         it: one ``scan_extrema`` launch over the group columns and the key's rank-encoded copy
         gives its count, smallest and largest rank per group, the row under each rank decodes
         them -- O(groups).  Without kernels, or with more groups than the device takes,
-        ``extrema_numpy`` does the same over the CPU selection.  ``partial``: the answer in the
-        form shards merge (``AggGroups.response``)."""
+        ``extrema_numpy`` does the same over the CPU selection.
+        A key that is asked a SUM or an AVG, whose histogram would pass ``SUMS_FROM_CELLS`` cells
+        and whose numbers share a scale (``Column.num_scale``: amounts, durations, points) gets,
+        unless ``hist``, one ``scan_sums`` launch over the group columns and its own id column
+        (``hip/group_sums.hip``; ``sums_numpy`` without kernels or past the device's groups):
+        exact integer sums per group, which ``AggGroups`` turns into ``reduce_hist``'s answer;
+        its COUNT / MIN / MAX come from the extrema path.  If a group's magnitudes reach 2^53
+        the sums prove nothing and the key's histogram answers as before.
+        ``partial``: the answer in the form shards merge (``AggGroups.response``)."""
         spec = parse_aggregate(q)
         # every referenced column first: one re-encode (source-backed) and one device upload
         self.ensure_columns(filter_paths(spec.filter) + spec.group_by + spec.keys)
@@ -1263,9 +1495,17 @@ class ColumnarIndex:
         ext_keys = [] if hist else [k for k in extrema_keys(spec)
                                     if gcells * (self._dict_size(self.col_of[k]) + 1) > from_cells]
         ext_dev = kernels is not None and gcells <= cap  # else the groups alone are past the device
+        # SUM / AVG keys past their own threshold (compared alone: the device's cap does not lower
+        # it) whose numbers share a scale that cannot wrap 64 bits over this many rows
+        sum_path = [] if hist else [k for k in sum_keys(spec)
+                                    if gcells * (self._dict_size(self.col_of[k]) + 1) > self.SUMS_FROM_CELLS
+                                    and self.columns[self.col_of[k]].num_scale(self.n) is not None]
+        # ... their COUNT / MIN / MAX then come from extrema, whatever EXTREMA_FROM_CELLS says
+        sum_ext = [k for k in sum_path if any(op in EXTREMA_OPS for op, kk in spec.aggs if kk == k)]
         dev = None
         if kernels is not None:
-            dev = (*self.mirror.program(prog, kernels, [self.col_of[k] for k in ext_keys] if ext_dev else ()), cap)
+            dev = (*self.mirror.program(prog, kernels, [self.col_of[k] for k in ext_keys + sum_ext] if ext_dev else (),
+                                        [self.col_of[k] for k in sum_path] if ext_dev else ()), cap)
         host_rows: list[np.ndarray] = []  # the CPU selection, made once when a histogram needs it
 
         def selection() -> np.ndarray:
@@ -1286,6 +1526,17 @@ class ColumnarIndex:
             cnt = cnt.cpu().numpy().view(np.uint32)
             cells = np.nonzero(cnt)[0]
             return cells, cnt[cells], lo.cpu().numpy().view(np.uint64)[cells], hi.cpu().numpy().view(np.uint64)[cells]
+
+        def sums(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+            """(cells, rows holding a number, sum of their m, sum of their |m|) of column ``kc``."""
+            if not ext_dev:
+                return self.sums_numpy(selection(), gcols, gdims, kc)
+            m = dev[0]
+            cnt, s, a = kernels.scan_sums(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims, kc,
+                                          m.nums[kc])
+            cnt = cnt.cpu().numpy().view(np.uint32)
+            cells = np.nonzero(cnt)[0]
+            return cells, cnt[cells], s.cpu().numpy()[cells], a.cpu().numpy().view(np.uint64)[cells]
 
         def histogram(cols: list[int]) -> tuple[np.ndarray, np.ndarray, list[int]]:
             """(non-zero cells, their counts, the axes' sizes) of the key columns ``cols``."""
@@ -1328,7 +1579,21 @@ class ColumnarIndex:
             groups.add_rows(tuple(value(c, s[i]) for c, s in zip(gcols, slots)), n)
         for key in spec.keys:
             kc = self.col_of[key]
-            if key in ext_keys:
+            summed = False
+            if key in sum_path:
+                cells, counts, s, a = sums(kc)
+                # a group whose magnitudes reach 2^53 proves nothing: the key's histogram answers.
+                # That fallback costs one pass more than before -- this launch, and for a key of
+                # ``sum_ext`` the rank-encoded copy uploaded above -- known only after the sums.
+                summed = not bool((a >= np.uint64(1 << 53)).any())
+                if summed:
+                    e = self.columns[kc].num_scale(self.n)[0]
+                    slots = decode(cells, gdims)
+                    for i, (n, si, ai) in enumerate(zip(counts.tolist(), s.tolist(), a.tolist())):
+                        groups.add_sums(tuple(value(c, sl[i]) for c, sl in zip(gcols, slots)), key, n, si, ai, e)
+                    if key not in sum_ext:
+                        continue
+            if key in ext_keys or summed:
                 cells, counts, lo, hi = extrema(kc)
                 slots = decode(cells, gdims)
                 vals = self.columns[kc].values

@@ -30,6 +30,14 @@ class RankColumn:
 
 
 @dataclass
+class NumTable:
+    """A column's scaled integers per dictionary id (``Column.nums``), kept on the device."""
+    buf: Any                # int64, grown by doubling
+    n: int = 0              # ids uploaded so far
+    epoch: int = -1         # Column.scale_epoch they were computed at
+
+
+@dataclass
 class Zone:
     """Zone map of one sort spec: per tile the live row with the smallest ordering key."""
     sort: Any
@@ -72,6 +80,8 @@ class DeviceMirror:
         self.ranks: dict[int, RankColumn] = {}
         self.rank_slot: dict[int, int] = {}   # column -> row of its rank copy in ``table``
         self.rank_cols: list[int] = []        # columns the last program read as ranks (``warm``)
+        self._nums: dict[int, NumTable] = {}
+        self.nums: dict[int, Any] = {}        # column -> id -> m on the device, of the last ``program``
         self.table: Any = None                # the column descriptor table of the last sync
         self.table_widths: np.ndarray | None = None
         self._tables: dict[tuple, Any] = {}   # descriptor tables by content: no upload per query
@@ -128,6 +138,7 @@ class DeviceMirror:
             self.seq = torch.from_numpy(ix.seq[:ix.cap].astype(np.int32)).to(dev)  # uint32 on device
             self.synced, self.cap = ix.n, ix.cap
             self.ranks, self.rank_slot, self._tables = {}, {}, {}
+            self._nums, self.nums = {}, {}
         else:
             lo, hi = self.synced, ix.n
             # the appended rows of every column, the sequence and the liveness words go up in
@@ -214,11 +225,37 @@ class DeviceMirror:
         cur.synced = ix.n
         return cur
 
-    def program(self, prog, kernels, rank_cols=()):
+    def _sync_num_table(self, kernels, col: int) -> Any:
+        """The device copy of ``Column.nums`` up to the dictionary's size: the new tail alone
+        while the scale holds, the whole table when it changed (``scale_epoch``) and after a
+        full re-upload."""
+        torch = kernels.torch
+        c = self.index.columns[col]
+        if c.num_scale() is None:
+            raise ValueError("the column's numbers share no scale")
+        n = len(c.values)
+        cur = self._nums.get(col)
+        if cur is None:
+            cur = self._nums[col] = NumTable(torch.empty(max(1024, 1 << max(0, n - 1).bit_length()),
+                                                         dtype=torch.int64, device=kernels.device))
+        if cur.epoch != c.scale_epoch or cur.n > n:
+            cur.n, cur.epoch = 0, c.scale_epoch
+        if cur.buf.numel() < n:
+            grown = torch.empty(1 << (n - 1).bit_length(), dtype=torch.int64, device=kernels.device)
+            grown[:cur.n] = cur.buf[:cur.n]
+            cur.buf = grown
+        if n > cur.n:
+            kernels.upload([(cur.buf.data_ptr() + 8 * cur.n, c.nums(cur.n, n))])
+            cur.n = n
+        return cur.buf[:n]
+
+    def program(self, prog, kernels, rank_cols=(), num_cols=()):
         """Sync for ``prog`` and return (mirror, program, bitmaps) ready for ``GpuKernels.select``
         (range leaves remapped to their rank-encoded columns).  ``rank_cols``: further columns to
         keep rank-encoded copies of (``rank_slot`` has their rows of the table): the value
-        columns of ``GpuKernels.scan_extrema``."""
+        columns of ``GpuKernels.scan_extrema``.  ``num_cols``: columns whose scaled-integer
+        tables (``Column.nums``) to keep on the device (``nums`` has them): the value columns
+        of ``GpuKernels.scan_sums``."""
         leaf = (prog.code[:, 0] == OP_LEAF) | (prog.code[:, 0] == OP_EQ) | (prog.code[:, 0] == OP_RANGE)
         if leaf.any() and int(prog.code[leaf, 1].max()) >= len(self.index.columns):
             raise ValueError("program references a column outside the index")
@@ -227,7 +264,10 @@ class DeviceMirror:
         rng = prog.code[:, 0] == OP_RANGE
         leaves = prog.code[rng, 1].tolist()
         self.rank_cols = leaves + [int(c) for c in rank_cols]
+        if any(not 0 <= c < len(self.index.columns) for c in num_cols):
+            raise ValueError("number column outside the index")
         self.sync(kernels, self.rank_cols)
+        self.nums = {int(c): self._sync_num_table(kernels, int(c)) for c in sorted(set(num_cols))}
         slots = tuple(sorted((c, self.rank_slot[c]) for c in set(leaves)))  # the program's own
         cached = prog.device
         if cached is not None and cached[0] == (slots, str(kernels.device)):

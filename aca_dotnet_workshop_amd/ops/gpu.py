@@ -54,6 +54,8 @@ def load_library(build: bool = True) -> ctypes.CDLL:
     lib.tt_launch_scan_extrema.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, P, P, I32, P]
     lib.tt_launch_scan_extrema.restype = ctypes.c_int
     lib.tt_extrema_max_lds_cells.restype = ctypes.c_int
+    lib.tt_launch_scan_sums.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, I64, P, P, P, I32, P]
+    lib.tt_launch_scan_sums.restype = ctypes.c_int
     lib.tt_launch_sort_keys.argtypes = [P, P, I64, P, I32, P, I32, P, I32, P, P, I32, P]
     lib.tt_launch_sort_keys.restype = ctypes.c_int
     lib.tt_sort_max_keys.restype = ctypes.c_int
@@ -440,6 +442,58 @@ class GpuKernels:
         if rc != 0:
             raise RuntimeError(f"tt_scan_extrema launch failed ({rc})")
         self.extrema_scans += 1
+        return out
+
+    sum_scans = 0  # tt_scan_sums launches
+
+    def scan_sums(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, value_col: int, nums,
+                  max_blocks: int = 0, out=None):
+        """Per group cell, over the live rows satisfying ``prog`` whose value is a number: (nums
+        int32 holding uint32, sum int64, abs int64 holding uint64) -- how many, the sum of their
+        scaled integers ``m`` and the sum of ``|m|``, filter and sums in one pass
+        (``hip/group_sums.hip`` tt_scan_sums).  ``keys`` / ``dims``: up to 2 group columns and
+        their dictionary sizes, cells as for ``scan_group``; ``value_col``: the row of ``table``
+        with the key's dictionary ids; ``nums``: device int64, the ``m`` of every id
+        (``Column.num_scale``), INT64_MIN where the value is no number; ids at or past its size
+        add nothing.  Integer atomics: the same buffers on every run.  ``out``: a zeroed (nums,
+        sum, abs) triple to add into instead of a new one.  ValueError when the cells exceed
+        ``tt_group_max_cells()``."""
+        torch = self.torch
+        keys, dims, value_col = [int(x) for x in keys], [int(x) for x in dims], int(value_col)
+        if len(keys) != len(dims) or len(keys) > 2:
+            raise ValueError("at most 2 group columns, one dictionary size each")
+        self._check_scan_args(table, live16, capacity, nrows, prog)
+        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
+            raise ValueError("group columns must be rows of the column table, dictionary sizes >= 0")
+        if not 0 <= value_col < table.shape[0]:
+            raise ValueError("the value column must be a row of the column table")
+        if nrows > 1 << 32:
+            raise ValueError("rows past 2^32 do not fit a cell's count")
+        if nums.dtype != torch.int64 or nums.ndim != 1 or not nums.is_contiguous() or nums.numel() > 1 << 31:
+            raise ValueError("the number table must be contiguous int64, one entry per dictionary id")
+        ncells = 1
+        for d in dims:
+            ncells *= d + 1
+        limit = int(self.lib.tt_group_max_cells())
+        n = min(ncells, limit)
+        if out is None:
+            out = (torch.zeros(n, dtype=torch.int32, device=self.device),
+                   torch.zeros(n, dtype=torch.int64, device=self.device),
+                   torch.zeros(n, dtype=torch.int64, device=self.device))
+        elif len(out) != 3 or out[0].dtype != torch.int32 or out[1].dtype != torch.int64 or \
+                out[2].dtype != torch.int64 or any(t.numel() < n for t in out):
+            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
+        rc = self.lib.tt_launch_scan_sums(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
+                                          prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
+                                          (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims), len(keys),
+                                          value_col, nums.data_ptr() if nums.numel() else None, nums.numel(),
+                                          out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                          max_blocks, self._stream())
+        if rc == -2:
+            raise ValueError(f"{ncells} group cells exceed the device limit of {limit}")
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_sums launch failed ({rc})")
+        self.sum_scans += 1
         return out
 
     def sort_keys(self, table, rows, specs, ranks, seq, seq_bits: int, hist=None, shift: int = 0):
