@@ -1411,21 +1411,26 @@ class ColumnarIndex:
     # with the device's cap (in production the two are equal).
     SUMS_FROM_CELLS = 1 << 22
 
+    def cells_of(self, rows: np.ndarray, cols: list[int], dims: list[int]) -> np.ndarray:
+        """The cell of each of ``rows`` over the key columns ``cols``: axis i has ``dims[i] + 1``
+        slots, slot ``dims[i]`` = path missing (the rule of group_cells, ``hip/scan_cells.h``)."""
+        cell = np.zeros(rows.size, dtype=np.int64)
+        for c, d in zip(cols, dims):
+            ids = self.ids[c, rows]
+            cell = cell * (d + 1) + np.where(ids < 0, d, ids)
+        return cell
+
     def sums_numpy(self, rows: np.ndarray, gcols: list[int], gdims: list[int],
                    kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """Host twin of ``hip/group_sums.hip`` over the selected ``rows``: (cells with a number
         in column ``kc``, how many rows hold one, the sum of their scaled integers m as int64, the
-        sum of |m| as uint64), the cell of a row as in ``aggregate``'s histograms of the group
-        columns.  Integer adds only (``reduceat``): exact, whatever the order."""
+        sum of |m| as uint64), cells by ``cells_of``.  Integer adds only (``reduceat``): exact in any order."""
         col = self.columns[kc]
         ids = self.ids[kc, rows]
         rows, ids = rows[ids >= 0], ids[ids >= 0]
         m = col.nums(0, len(col.values))[ids] if ids.size else np.zeros(0, dtype=np.int64)
         rows, m = rows[m != NOT_A_NUMBER], m[m != NOT_A_NUMBER]
-        cell = np.zeros(rows.size, dtype=np.int64)
-        for c, d in zip(gcols, gdims):
-            g = self.ids[c, rows]
-            cell = cell * (d + 1) + np.where(g < 0, d, g)
+        cell = self.cells_of(rows, gcols, gdims)
         if not cell.size:
             return cell, cell, m, m.astype(np.uint64)
         order = np.argsort(cell, kind="stable")
@@ -1443,13 +1448,10 @@ class ColumnarIndex:
                       kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """Host twin of ``hip/group_extrema.hip`` over the selected ``rows``: (cells with a
         defined value of column ``kc``, their row counts, smallest and largest ``rank << 32 |
-        row``), the cell of a row as in ``aggregate``'s histograms of the group columns."""
+        row``), cells by ``cells_of`` over the group columns."""
         ids = self.ids[kc, rows]
         rows, ids = rows[ids >= 0], ids[ids >= 0]
-        cell = np.zeros(rows.size, dtype=np.int64)
-        for c, d in zip(gcols, gdims):
-            g = self.ids[c, rows]
-            cell = cell * (d + 1) + np.where(g < 0, d, g)
+        cell = self.cells_of(rows, gcols, gdims)
         ranks = self.columns[kc].ranks()[ids] if ids.size else np.zeros(0, dtype=np.int64)
         key = (ranks.astype(np.uint64) << np.uint64(32)) | rows.astype(np.uint64)
         order = np.lexsort((key, cell))  # by cell, then by key: a cell's extrema at its ends
@@ -1516,6 +1518,13 @@ class ColumnarIndex:
                     host_rows.append(self.select_numpy(prog))
             return host_rows[0]
 
+        def counted(cnt, *words) -> tuple[np.ndarray, ...]:
+            """(non-zero cells, their counts, each of ``words`` at those cells) of a device vector
+            of uint32 counts held as int32; ``words``: (device vector, the dtype to read it as)."""
+            cnt = cnt.cpu().numpy().view(np.uint32)
+            cells = np.nonzero(cnt)[0]
+            return (cells, cnt[cells], *(w.cpu().numpy().view(t)[cells] for w, t in words))
+
         def extrema(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
             """(cells, rows with a value, smallest, largest rank << 32 | row) of column ``kc``."""
             if not ext_dev:
@@ -1523,9 +1532,7 @@ class ColumnarIndex:
             m = dev[0]
             cnt, lo, hi = kernels.scan_extrema(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims,
                                                m.rank_slot[kc])
-            cnt = cnt.cpu().numpy().view(np.uint32)
-            cells = np.nonzero(cnt)[0]
-            return cells, cnt[cells], lo.cpu().numpy().view(np.uint64)[cells], hi.cpu().numpy().view(np.uint64)[cells]
+            return counted(cnt, (lo, np.uint64), (hi, np.uint64))
 
         def sums(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
             """(cells, rows holding a number, sum of their m, sum of their |m|) of column ``kc``."""
@@ -1534,9 +1541,7 @@ class ColumnarIndex:
             m = dev[0]
             cnt, s, a = kernels.scan_sums(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims, kc,
                                           m.nums[kc])
-            cnt = cnt.cpu().numpy().view(np.uint32)
-            cells = np.nonzero(cnt)[0]
-            return cells, cnt[cells], s.cpu().numpy()[cells], a.cpu().numpy().view(np.uint64)[cells]
+            return counted(cnt, (s, np.int64), (a, np.uint64))
 
         def histogram(cols: list[int]) -> tuple[np.ndarray, np.ndarray, list[int]]:
             """(non-zero cells, their counts, the axes' sizes) of the key columns ``cols``."""
@@ -1545,15 +1550,9 @@ class ColumnarIndex:
             if ncells >= 1 << 62:
                 raise Unsupported("aggregate key space too large")
             if dev is not None and ncells <= dev[3]:
-                counts = kernels.scan_group(dev[0].table, dev[0].live, self.cap, self.n, dev[1], dev[2],
-                                            cols, dims).cpu().numpy().view(np.uint32)
-                cells = np.nonzero(counts)[0]
-                return cells, counts[cells], dims
-            selection()
-            cell = np.zeros(host_rows[0].size, dtype=np.int64)
-            for c, d in zip(cols, dims):
-                ids = self.ids[c, host_rows[0]]
-                cell = cell * (d + 1) + np.where(ids < 0, d, ids)
+                return *counted(kernels.scan_group(dev[0].table, dev[0].live, self.cap, self.n, dev[1], dev[2],
+                                                   cols, dims)), dims
+            cell = self.cells_of(selection(), cols, dims)
             if ncells <= self.HOST_MAX_CELLS:
                 counts = np.bincount(cell, minlength=ncells)
                 cells = np.nonzero(counts)[0]

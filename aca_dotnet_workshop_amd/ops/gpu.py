@@ -361,6 +361,34 @@ class GpuKernels:
             raise RuntimeError(f"tt_group_count launch failed ({rc})")
         return counts[:ngroups]
 
+    def _group_args(self, table, live16, capacity: int, nrows: int, prog, keys, dims, max_keys: int, what: str,
+                    value_col=None, out=None, fills=None):
+        """What the grouped scans check alike: the scan's own arguments, ``keys`` / ``dims`` (at
+        most ``max_keys``, called ``what`` in a refusal) and ``value_col`` against ``table``.
+        Returns (keys, dims, cells, the device's cell limit, outputs): with ``fills`` the (int32,
+        int64, int64) triple of one element per cell, ``out`` checked or a new one so filled."""
+        torch = self.torch
+        keys, dims = [int(x) for x in keys], [int(x) for x in dims]
+        if len(keys) != len(dims) or len(keys) > max_keys:
+            raise ValueError(f"at most {max_keys} {what} columns, one dictionary size each")
+        self._check_scan_args(table, live16, capacity, nrows, prog)
+        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
+            raise ValueError(f"{what} columns must be rows of the column table, dictionary sizes >= 0")
+        if value_col is not None and not 0 <= value_col < table.shape[0]:
+            raise ValueError("the value column must be a row of the column table")
+        ncells = 1
+        for d in dims:
+            ncells *= d + 1
+        limit = int(self.lib.tt_group_max_cells())
+        n = min(ncells, limit)
+        dtypes = (torch.int32, torch.int64, torch.int64)
+        if fills is not None and out is None:
+            out = tuple(torch.full((n,), f, dtype=t, device=self.device) if f else
+                        torch.zeros(n, dtype=t, device=self.device) for f, t in zip(fills, dtypes))
+        elif fills is not None and (len(out) != 3 or any(o.dtype != t or o.numel() < n for o, t in zip(out, dtypes))):
+            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
+        return keys, dims, ncells, limit, out
+
     def scan_group(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, max_blocks: int = 0,
                    counts=None):
         """Histogram (device int32 holding uint32 counts, ``prod(dims[i] + 1)`` cells) of the key
@@ -371,16 +399,7 @@ class GpuKernels:
         ``capacity`` as for ``select``.  ``counts``: a zeroed tensor to add into instead of a
         new one.  ValueError when the cells exceed ``tt_group_max_cells()``."""
         torch = self.torch
-        keys, dims = [int(x) for x in keys], [int(x) for x in dims]
-        if len(keys) != len(dims) or len(keys) > 3:
-            raise ValueError("at most 3 key columns, one dictionary size each")
-        self._check_scan_args(table, live16, capacity, nrows, prog)
-        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
-            raise ValueError("key columns must be rows of the column table, dictionary sizes >= 0")
-        ncells = 1
-        for d in dims:
-            ncells *= d + 1
-        limit = int(self.lib.tt_group_max_cells())
+        keys, dims, ncells, limit, _ = self._group_args(table, live16, capacity, nrows, prog, keys, dims, 3, "key")
         if counts is None:
             counts = torch.zeros(min(ncells, limit), dtype=torch.int32, device=self.device)
         elif counts.dtype != torch.int32 or counts.numel() < min(ncells, limit):
@@ -409,29 +428,11 @@ class GpuKernels:
         all-ones code = undefined.  ``lo`` / ``hi`` of a cell mean something only where its count
         is not 0.  ``out``: a (counts, lo, hi) triple initialised to 0 / -1 / 0 to reduce into
         instead of a new one.  ValueError when the cells exceed ``tt_group_max_cells()``."""
-        torch = self.torch
-        keys, dims, value_col = [int(x) for x in keys], [int(x) for x in dims], int(value_col)
-        if len(keys) != len(dims) or len(keys) > 2:
-            raise ValueError("at most 2 group columns, one dictionary size each")
-        self._check_scan_args(table, live16, capacity, nrows, prog)
-        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
-            raise ValueError("group columns must be rows of the column table, dictionary sizes >= 0")
-        if not 0 <= value_col < table.shape[0]:
-            raise ValueError("the value column must be a row of the column table")
+        value_col = int(value_col)
+        keys, dims, ncells, limit, out = self._group_args(table, live16, capacity, nrows, prog, keys, dims, 2, "group",
+                                                          value_col, out, (0, -1, 0))
         if nrows > 1 << 32:
             raise ValueError("rows past 2^32 do not fit next to the code")
-        ncells = 1
-        for d in dims:
-            ncells *= d + 1
-        limit = int(self.lib.tt_group_max_cells())
-        n = min(ncells, limit)
-        if out is None:
-            out = (torch.zeros(n, dtype=torch.int32, device=self.device),
-                   torch.full((n,), -1, dtype=torch.int64, device=self.device),
-                   torch.zeros(n, dtype=torch.int64, device=self.device))
-        elif len(out) != 3 or out[0].dtype != torch.int32 or out[1].dtype != torch.int64 or \
-                out[2].dtype != torch.int64 or any(t.numel() < n for t in out):
-            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
         rc = self.lib.tt_launch_scan_extrema(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
                                              prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
                                              (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims), len(keys),
@@ -459,30 +460,13 @@ class GpuKernels:
         sum, abs) triple to add into instead of a new one.  ValueError when the cells exceed
         ``tt_group_max_cells()``."""
         torch = self.torch
-        keys, dims, value_col = [int(x) for x in keys], [int(x) for x in dims], int(value_col)
-        if len(keys) != len(dims) or len(keys) > 2:
-            raise ValueError("at most 2 group columns, one dictionary size each")
-        self._check_scan_args(table, live16, capacity, nrows, prog)
-        if any(not 0 <= c < table.shape[0] for c in keys) or any(d < 0 for d in dims):
-            raise ValueError("group columns must be rows of the column table, dictionary sizes >= 0")
-        if not 0 <= value_col < table.shape[0]:
-            raise ValueError("the value column must be a row of the column table")
+        value_col = int(value_col)
+        keys, dims, ncells, limit, out = self._group_args(table, live16, capacity, nrows, prog, keys, dims, 2, "group",
+                                                          value_col, out, (0, 0, 0))
         if nrows > 1 << 32:
             raise ValueError("rows past 2^32 do not fit a cell's count")
         if nums.dtype != torch.int64 or nums.ndim != 1 or not nums.is_contiguous() or nums.numel() > 1 << 31:
             raise ValueError("the number table must be contiguous int64, one entry per dictionary id")
-        ncells = 1
-        for d in dims:
-            ncells *= d + 1
-        limit = int(self.lib.tt_group_max_cells())
-        n = min(ncells, limit)
-        if out is None:
-            out = (torch.zeros(n, dtype=torch.int32, device=self.device),
-                   torch.zeros(n, dtype=torch.int64, device=self.device),
-                   torch.zeros(n, dtype=torch.int64, device=self.device))
-        elif len(out) != 3 or out[0].dtype != torch.int32 or out[1].dtype != torch.int64 or \
-                out[2].dtype != torch.int64 or any(t.numel() < n for t in out):
-            raise ValueError("outputs must be (int32, int64, int64), one element per cell")
         rc = self.lib.tt_launch_scan_sums(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
                                           prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
                                           (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims), len(keys),

@@ -1,6 +1,7 @@
-// Shared device code of the gfx950 query kernels (query_scan.hip, group_agg.hip, sort_keys.hip,
-// page_topk.hip): the column descriptor table, the narrow-code loads (ops/codes.py is the host's
-// side of that layout) and the postfix filter interpreter over 16-row groups.
+// Shared device code of the gfx950 query kernels (query_scan.hip, sort_keys.hip, page_topk.hip and,
+// through scan_cells.h, group_agg.hip, group_extrema.hip, group_sums.hip): the column descriptor
+// table, the narrow-code loads (ops/codes.py is the host's side of that layout) and the postfix
+// filter interpreter over 16-row groups.
 // See query_scan.hip for the data model.
 #pragma once
 #include <hip/hip_runtime.h>
