@@ -1411,6 +1411,23 @@ class ColumnarIndex:
     # with the device's cap (in production the two are equal).
     SUMS_FROM_CELLS = 1 << 22
 
+    # A histogram, extrema or sums request whose dense cells are past the device's cap
+    # (``tt_group_max_cells()``: a product of dictionary sizes, passed long before the groups that
+    # occur are many) keeps its cells in a hash table on the device instead
+    # (``hip/sparse_cells.h``; ``GpuKernels.scan_sparse`` / ``scan_extrema_sparse`` /
+    # ``scan_sums_sparse``), from this many rows on: below it the host selection answers as before.
+    # The measured crossover (profiles/group_sparse.md): the hashed scan's fixed cost -- filling the
+    # table, reading its status, compacting it -- loses to ``select_native`` + ``np.unique`` at
+    # 20,000 to 40,000 rows, is level with it at 50,000 and wins from 70,000 on at every
+    # selectivity and grouping measured.  Never below 20,000, ``TT_QUERY_ACCEL_MIN_DOCS``'s default:
+    # below that production does not use the accelerator at all.
+    SPARSE_FROM_ROWS = 50_000
+    # The table takes the next power of two of slots >= 2 x min(cells, rows) -- load <= 0.5, it
+    # cannot overflow -- up to this many: a memory choice (12 bytes per slot with counts, 768 MiB;
+    # 28 bytes with value words, 1.75 GiB).  Capped, it can overflow: the kernels then say so and
+    # the host answers that request.
+    SPARSE_MAX_SLOTS = 1 << 26
+
     def cells_of(self, rows: np.ndarray, cols: list[int], dims: list[int]) -> np.ndarray:
         """The cell of each of ``rows`` over the key columns ``cols``: axis i has ``dims[i] + 1``
         slots, slot ``dims[i]`` = path missing (the rule of group_cells, ``hip/scan_cells.h``)."""
@@ -1484,6 +1501,12 @@ class ColumnarIndex:
         exact integer sums per group, which ``AggGroups`` turns into ``reduce_hist``'s answer;
         its COUNT / MIN / MAX come from the extrema path.  If a group's magnitudes reach 2^53
         the sums prove nothing and the key's histogram answers as before.
+        A histogram, extrema or sums request past the device's cap of dense cells goes, from
+        ``SPARSE_FROM_ROWS`` rows on and with kernels that have them, through the hashed scans
+        (``scan_sparse`` / ``scan_extrema_sparse`` / ``scan_sums_sparse``): the same (cell, count,
+        words) as the host's ``np.unique``, of the cells that occur, with no host selection.  A
+        table capped at ``SPARSE_MAX_SLOTS`` that overflows answers None and that request alone
+        falls through to the host code.
         ``partial``: the answer in the form shards merge (``AggGroups.response``)."""
         spec = parse_aggregate(q)
         # every referenced column first: one re-encode (source-backed) and one device upload
@@ -1496,7 +1519,13 @@ class ColumnarIndex:
         from_cells = self.EXTREMA_FROM_CELLS if cap is None else min(self.EXTREMA_FROM_CELLS, cap)
         ext_keys = [] if hist else [k for k in extrema_keys(spec)
                                     if gcells * (self._dict_size(self.col_of[k]) + 1) > from_cells]
-        ext_dev = kernels is not None and gcells <= cap  # else the groups alone are past the device
+        ext_dev = kernels is not None and gcells <= cap  # else the groups alone are past the dense cells
+        # ... and then go through the hashed cells, when the kernels have them (a stand-in device
+        # without them keeps the host plan) and the collection is worth a launch
+        sparse = kernels is not None and self.n >= self.SPARSE_FROM_ROWS and all(
+            getattr(kernels, name, None) is not None
+            for name in ("scan_sparse", "scan_extrema_sparse", "scan_sums_sparse"))
+        val_dev = ext_dev or (sparse and gcells < 1 << 62)  # the value kernels run on the device
         # SUM / AVG keys past their own threshold (compared alone: the device's cap does not lower
         # it) whose numbers share a scale that cannot wrap 64 bits over this many rows
         sum_path = [] if hist else [k for k in sum_keys(spec)
@@ -1506,8 +1535,8 @@ class ColumnarIndex:
         sum_ext = [k for k in sum_path if any(op in EXTREMA_OPS for op, kk in spec.aggs if kk == k)]
         dev = None
         if kernels is not None:
-            dev = (*self.mirror.program(prog, kernels, [self.col_of[k] for k in ext_keys + sum_ext] if ext_dev else (),
-                                        [self.col_of[k] for k in sum_path] if ext_dev else ()), cap)
+            dev = (*self.mirror.program(prog, kernels, [self.col_of[k] for k in ext_keys + sum_ext] if val_dev else (),
+                                        [self.col_of[k] for k in sum_path] if val_dev else ()), cap)
         host_rows: list[np.ndarray] = []  # the CPU selection, made once when a histogram needs it
 
         def selection() -> np.ndarray:
@@ -1525,9 +1554,29 @@ class ColumnarIndex:
             cells = np.nonzero(cnt)[0]
             return (cells, cnt[cells], *(w.cpu().numpy().view(t)[cells] for w, t in words))
 
+        def slots_for(ncells: int) -> int:
+            """The hash table's slots for a space of ``ncells`` cells over this collection."""
+            need = 2 * max(1, min(ncells, self.n))
+            return min(self.SPARSE_MAX_SLOTS, max(2, 1 << (need - 1).bit_length()))
+
+        def hashed(got, *types) -> tuple[np.ndarray, ...] | None:
+            """A hashed scan's (cells, counts, words...) on the host; None (the table overflowed:
+            the host answers) stays None."""
+            if got is None:
+                return None
+            cells, cnt, *words = (t.cpu().numpy() for t in got)
+            return (cells, cnt.view(np.uint32), *(w.view(t) for w, t in zip(words, types)))
+
         def extrema(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
             """(cells, rows with a value, smallest, largest rank << 32 | row) of column ``kc``."""
             if not ext_dev:
+                if val_dev:
+                    m = dev[0]
+                    got = hashed(kernels.scan_extrema_sparse(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols,
+                                                             gdims, m.rank_slot[kc], slots_for(gcells)),
+                                 np.uint64, np.uint64)
+                    if got is not None:
+                        return got
                 return self.extrema_numpy(selection(), gcols, gdims, kc)
             m = dev[0]
             cnt, lo, hi = kernels.scan_extrema(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims,
@@ -1537,6 +1586,13 @@ class ColumnarIndex:
         def sums(kc: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
             """(cells, rows holding a number, sum of their m, sum of their |m|) of column ``kc``."""
             if not ext_dev:
+                if val_dev:
+                    m = dev[0]
+                    got = hashed(kernels.scan_sums_sparse(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols,
+                                                          gdims, kc, m.nums[kc], slots_for(gcells)),
+                                 np.int64, np.uint64)
+                    if got is not None:
+                        return got
                 return self.sums_numpy(selection(), gcols, gdims, kc)
             m = dev[0]
             cnt, s, a = kernels.scan_sums(m.table, m.live, self.cap, self.n, dev[1], dev[2], gcols, gdims, kc,
@@ -1552,6 +1608,11 @@ class ColumnarIndex:
             if dev is not None and ncells <= dev[3]:
                 return *counted(kernels.scan_group(dev[0].table, dev[0].live, self.cap, self.n, dev[1], dev[2],
                                                    cols, dims)), dims
+            if sparse:
+                got = hashed(kernels.scan_sparse(dev[0].table, dev[0].live, self.cap, self.n, dev[1], dev[2],
+                                                 cols, dims, slots_for(ncells)))
+                if got is not None:
+                    return *got, dims
             cell = self.cells_of(selection(), cols, dims)
             if ncells <= self.HOST_MAX_CELLS:
                 counts = np.bincount(cell, minlength=ncells)

@@ -56,6 +56,14 @@ def load_library(build: bool = True) -> ctypes.CDLL:
     lib.tt_extrema_max_lds_cells.restype = ctypes.c_int
     lib.tt_launch_scan_sums.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, I64, P, P, P, I32, P]
     lib.tt_launch_scan_sums.restype = ctypes.c_int
+    lib.tt_launch_scan_sparse.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, P, P, I64, P, I32, P]
+    lib.tt_launch_scan_sparse.restype = ctypes.c_int
+    lib.tt_sparse_max_probes.restype = ctypes.c_int
+    lib.tt_launch_scan_extrema_sparse.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, P, P, P, I64, P, I32, P]
+    lib.tt_launch_scan_extrema_sparse.restype = ctypes.c_int
+    lib.tt_launch_scan_sums_sparse.argtypes = [P, I64, P, P, I32, P, I32, P, P, I32, I32, P, I64, P, P, P, P, I64, P,
+                                               I32, P]
+    lib.tt_launch_scan_sums_sparse.restype = ctypes.c_int
     lib.tt_launch_sort_keys.argtypes = [P, P, I64, P, I32, P, I32, P, I32, P, P, I32, P]
     lib.tt_launch_sort_keys.restype = ctypes.c_int
     lib.tt_sort_max_keys.restype = ctypes.c_int
@@ -362,11 +370,13 @@ class GpuKernels:
         return counts[:ngroups]
 
     def _group_args(self, table, live16, capacity: int, nrows: int, prog, keys, dims, max_keys: int, what: str,
-                    value_col=None, out=None, fills=None):
+                    value_col=None, out=None, fills=None, dense: bool = True):
         """What the grouped scans check alike: the scan's own arguments, ``keys`` / ``dims`` (at
         most ``max_keys``, called ``what`` in a refusal) and ``value_col`` against ``table``.
         Returns (keys, dims, cells, the device's cell limit, outputs): with ``fills`` the (int32,
-        int64, int64) triple of one element per cell, ``out`` checked or a new one so filled."""
+        int64, int64) triple of one element per cell, ``out`` checked or a new one so filled.
+        ``dense=False`` (the hashed scans, whose outputs follow their slots): the limit is the
+        2^62 cells a 64-bit cell takes, not ``tt_group_max_cells()``."""
         torch = self.torch
         keys, dims = [int(x) for x in keys], [int(x) for x in dims]
         if len(keys) != len(dims) or len(keys) > max_keys:
@@ -379,7 +389,7 @@ class GpuKernels:
         ncells = 1
         for d in dims:
             ncells *= d + 1
-        limit = int(self.lib.tt_group_max_cells())
+        limit = int(self.lib.tt_group_max_cells()) if dense else (1 << 62) - 1
         n = min(ncells, limit)
         dtypes = (torch.int32, torch.int64, torch.int64)
         if fills is not None and out is None:
@@ -479,6 +489,106 @@ class GpuKernels:
             raise RuntimeError(f"tt_scan_sums launch failed ({rc})")
         self.sum_scans += 1
         return out
+
+    sparse_scans = 0  # tt_scan_sparse / tt_scan_extrema_sparse / tt_scan_sums_sparse launches
+
+    def _sparse_args(self, table, live16, capacity: int, nrows: int, prog, keys, dims, max_keys: int, what: str,
+                     slots: int, value_col=None):
+        """The hashed scans' checks (``_group_args`` without the dense limit, ``slots`` a power of
+        two) and their table: (keys, dims, cells, table keys set to all-ones, a zeroed status word)."""
+        torch = self.torch
+        keys, dims, ncells, limit, _ = self._group_args(table, live16, capacity, nrows, prog, keys, dims, max_keys,
+                                                        what, value_col, dense=False)
+        slots = int(slots)
+        if slots < 2 or slots > 1 << 31 or slots & (slots - 1):
+            raise ValueError("the hash table takes a power of two of slots, 2 to 2^31")
+        if nrows > 1 << 32:
+            raise ValueError("rows past 2^32 do not fit a cell's count")
+        if ncells > limit:
+            raise ValueError(f"{ncells} group cells do not fit a 64-bit cell")
+        return (keys, dims, ncells, torch.full((slots,), -1, dtype=torch.int64, device=self.device),
+                torch.zeros(1, dtype=torch.int32, device=self.device))
+
+    def _sparse_result(self, table_keys, status, counts, *words):
+        """The occupied slots of a hashed scan, compacted on the device and sorted by cell: (cells
+        int64, counts, each of ``words``); None when the scan set ``status`` (a probe reached its
+        bound: the table was too full and rows were dropped)."""
+        torch = self.torch
+        self.sparse_scans += 1
+        if int(status.item()):
+            return None
+        slots = torch.nonzero(counts).flatten()
+        cells, order = torch.sort(table_keys[slots])
+        slots = slots[order]
+        return (cells, counts[slots], *(w[slots] for w in words))
+
+    def scan_sparse(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, slots: int,
+                    max_blocks: int = 0):
+        """The histogram of ``scan_group`` for a cell space of any size below 2^62, through a hash
+        table of ``slots`` slots (a power of two) in device memory (``hip/group_sparse.hip``
+        tt_scan_sparse): (cells int64 ascending, counts int32 holding uint32) of the cells that
+        occur, both on the device; cells as ``scan_group``'s, in 64 bits.  None when the table
+        was too full for the cells that occur (``slots`` of at least twice their number never
+        is)."""
+        keys, dims, _, tkeys, status = self._sparse_args(table, live16, capacity, nrows, prog, keys, dims, 3, "key",
+                                                         slots)
+        counts = self.torch.zeros(int(slots), dtype=self.torch.int32, device=self.device)
+        rc = self.lib.tt_launch_scan_sparse(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
+                                            prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
+                                            (ctypes.c_int32 * 3)(*keys), (ctypes.c_int32 * 3)(*dims), len(keys),
+                                            tkeys.data_ptr(), counts.data_ptr(), int(slots), status.data_ptr(),
+                                            max_blocks, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_sparse launch failed ({rc})")
+        return self._sparse_result(tkeys, status, counts)
+
+    def scan_extrema_sparse(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims,
+                            value_col: int, slots: int, max_blocks: int = 0):
+        """``scan_extrema`` for a group space of any size below 2^62, through a hash table of
+        ``slots`` slots (``hip/group_extrema.hip`` tt_scan_extrema_sparse): (cells int64
+        ascending, counts, lo, hi) of the cells with a defined value, on the device; None when
+        the table was too full."""
+        value_col = int(value_col)
+        keys, dims, _, tkeys, status = self._sparse_args(table, live16, capacity, nrows, prog, keys, dims, 2, "group",
+                                                         slots, value_col)
+        torch, n = self.torch, int(slots)
+        out = (torch.zeros(n, dtype=torch.int32, device=self.device),
+               torch.full((n,), -1, dtype=torch.int64, device=self.device),
+               torch.zeros(n, dtype=torch.int64, device=self.device))
+        rc = self.lib.tt_launch_scan_extrema_sparse(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
+                                                    prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
+                                                    (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims),
+                                                    len(keys), value_col, out[0].data_ptr(), out[1].data_ptr(),
+                                                    out[2].data_ptr(), tkeys.data_ptr(), n, status.data_ptr(),
+                                                    max_blocks, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_extrema_sparse launch failed ({rc})")
+        return self._sparse_result(tkeys, status, *out)
+
+    def scan_sums_sparse(self, table, live16, capacity: int, nrows: int, prog, bitmaps, keys, dims, value_col: int,
+                         nums, slots: int, max_blocks: int = 0):
+        """``scan_sums`` for a group space of any size below 2^62, through a hash table of
+        ``slots`` slots (``hip/group_sums.hip`` tt_scan_sums_sparse): (cells int64 ascending,
+        nums, sum, abs) of the cells that hold a number, on the device; None when the table was
+        too full."""
+        value_col = int(value_col)
+        keys, dims, _, tkeys, status = self._sparse_args(table, live16, capacity, nrows, prog, keys, dims, 2, "group",
+                                                         slots, value_col)
+        torch, n = self.torch, int(slots)
+        if nums.dtype != torch.int64 or nums.ndim != 1 or not nums.is_contiguous() or nums.numel() > 1 << 31:
+            raise ValueError("the number table must be contiguous int64, one entry per dictionary id")
+        out = (torch.zeros(n, dtype=torch.int32, device=self.device),
+               torch.zeros(n, dtype=torch.int64, device=self.device),
+               torch.zeros(n, dtype=torch.int64, device=self.device))
+        rc = self.lib.tt_launch_scan_sums_sparse(table.data_ptr(), nrows, live16.data_ptr(), prog.data_ptr(),
+                                                 prog.shape[0], bitmaps.data_ptr(), bitmaps.numel(),
+                                                 (ctypes.c_int32 * 2)(*keys), (ctypes.c_int32 * 2)(*dims), len(keys),
+                                                 value_col, nums.data_ptr() if nums.numel() else None, nums.numel(),
+                                                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                 tkeys.data_ptr(), n, status.data_ptr(), max_blocks, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"tt_scan_sums_sparse launch failed ({rc})")
+        return self._sparse_result(tkeys, status, *out)
 
     def sort_keys(self, table, rows, specs, ranks, seq, seq_bits: int, hist=None, shift: int = 0):
         """Packed 63-bit ordering keys (int64) for ``rows`` (int32, device): see

@@ -99,3 +99,40 @@ extern "C" int tt_launch_scan_extrema(const void* cols, int64_t nrows, const uin
 }
 
 extern "C" int tt_extrema_max_lds_cells() { return kMaxLdsCells; }
+
+// The same reduction over a sparse group space: the cells in a hash table (kHashedCells of
+// scan_reduce.h, sparse_cells.h), counts / lo / hi indexed by slot.
+__global__ void __launch_bounds__(kScanBlock)
+tt_scan_extrema_sparse(const ColumnDesc* __restrict__ cols,
+                       int64_t nrows, int64_t tiles,
+                       const uint16_t* __restrict__ live,      // 1 bit per row, row order
+                       const int32_t* __restrict__ prog, int32_t prog_len,
+                       const uint32_t* __restrict__ bitmaps, int32_t bitmap_words,
+                       GroupKeys gk,
+                       uint32_t* __restrict__ counts, uint64_t* __restrict__ lo, uint64_t* __restrict__ hi,
+                       uint64_t* __restrict__ table_keys, uint32_t mask, uint32_t* __restrict__ status) {
+  scan_reduce<Extrema, kHashedCells>(cols, nrows, tiles, live, prog, prog_len, bitmaps, bitmap_words, gk, 0, {},
+                                     counts, lo, hi, table_keys, mask, status);
+}
+
+// As tt_launch_scan_extrema, for any cell space below 2^62 (-2 at or past it).  `table_keys`:
+// `slots` uint64 set to all-ones, `slots` a power of two in [2, 2^31]; `counts` / `lo` / `hi` hold
+// `slots` elements initialised to 0 / all-ones / 0 and are indexed by slot; `status`: one zeroed
+// uint32, non-zero afterwards when the table was too full (discard the answer).
+extern "C" int tt_launch_scan_extrema_sparse(const void* cols, int64_t nrows, const uint16_t* live,
+                                             const int32_t* prog, int32_t prog_len, const uint32_t* bitmaps,
+                                             int32_t bitmap_words, const int32_t* keys, const int32_t* dims,
+                                             int32_t nkeys, int32_t value_col, uint32_t* counts, uint64_t* lo,
+                                             uint64_t* hi, uint64_t* table_keys, int64_t slots, uint32_t* status,
+                                             int32_t max_blocks, hipStream_t stream) {
+  if (!counts || !lo || !hi || !table_keys || !status) return -1;
+  ReducePlan p;
+  if (const int rc = plan_reduce_sparse(nrows, prog_len, bitmap_words, keys, dims, nkeys, value_col, slots,
+                                        max_blocks, p);
+      rc || !p.tiles)
+    return rc;
+  hipLaunchKernelGGL(tt_scan_extrema_sparse, dim3((unsigned)p.blocks), dim3(kScanBlock), p.lds, stream,
+                     reinterpret_cast<const ColumnDesc*>(cols), nrows, p.tiles, live, prog, prog_len, bitmaps,
+                     bitmap_words, p.gk, counts, lo, hi, table_keys, (uint32_t)(slots - 1), status);
+  return (int)hipGetLastError();
+}

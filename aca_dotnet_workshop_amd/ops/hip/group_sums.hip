@@ -99,3 +99,43 @@ extern "C" int tt_launch_scan_sums(const void* cols, int64_t nrows, const uint16
                      bitmap_words, p.gk, p.ncells, nums, (uint32_t)nvalues, cnt, sum, abs);
   return (int)hipGetLastError();
 }
+
+// The same sums over a sparse group space: the cells in a hash table (kHashedCells of
+// scan_reduce.h, sparse_cells.h), cnt / sum / abs indexed by slot.
+__global__ void __launch_bounds__(kScanBlock)
+tt_scan_sums_sparse(const ColumnDesc* __restrict__ cols,
+                    int64_t nrows, int64_t tiles,
+                    const uint16_t* __restrict__ live,      // 1 bit per row, row order
+                    const int32_t* __restrict__ prog, int32_t prog_len,
+                    const uint32_t* __restrict__ bitmaps, int32_t bitmap_words,
+                    GroupKeys gk,
+                    const int64_t* __restrict__ nums, uint32_t nvalues,   // id -> m
+                    uint32_t* __restrict__ cnt, uint64_t* __restrict__ sum, uint64_t* __restrict__ abs,
+                    uint64_t* __restrict__ table_keys, uint32_t mask, uint32_t* __restrict__ status) {
+  scan_reduce<Sums, kHashedCells>(cols, nrows, tiles, live, prog, prog_len, bitmaps, bitmap_words, gk, 0,
+                                  {nums, nvalues}, cnt, sum, abs, table_keys, mask, status);
+}
+
+// As tt_launch_scan_sums, for any cell space below 2^62 (-2 at or past it).  `table_keys`: `slots`
+// uint64 set to all-ones, `slots` a power of two in [2, 2^31]; `cnt` / `sum` / `abs` hold `slots`
+// zeroed elements and are indexed by slot; `status`: one zeroed uint32, non-zero afterwards when
+// the table was too full (discard the answer).
+extern "C" int tt_launch_scan_sums_sparse(const void* cols, int64_t nrows, const uint16_t* live, const int32_t* prog,
+                                          int32_t prog_len, const uint32_t* bitmaps, int32_t bitmap_words,
+                                          const int32_t* keys, const int32_t* dims, int32_t nkeys, int32_t value_col,
+                                          const int64_t* nums, int64_t nvalues, uint32_t* cnt, uint64_t* sum,
+                                          uint64_t* abs, uint64_t* table_keys, int64_t slots, uint32_t* status,
+                                          int32_t max_blocks, hipStream_t stream) {
+  if (nvalues < 0 || nvalues > (int64_t)1 << 31 || (nvalues > 0 && nums == nullptr)) return -1;
+  if (!cnt || !sum || !abs || !table_keys || !status) return -1;
+  ReducePlan p;
+  if (const int rc = plan_reduce_sparse(nrows, prog_len, bitmap_words, keys, dims, nkeys, value_col, slots,
+                                        max_blocks, p);
+      rc || !p.tiles)
+    return rc;
+  hipLaunchKernelGGL(tt_scan_sums_sparse, dim3((unsigned)p.blocks), dim3(kScanBlock), p.lds, stream,
+                     reinterpret_cast<const ColumnDesc*>(cols), nrows, p.tiles, live, prog, prog_len, bitmaps,
+                     bitmap_words, p.gk, nums, (uint32_t)nvalues, cnt, sum, abs, table_keys, (uint32_t)(slots - 1),
+                     status);
+  return (int)hipGetLastError();
+}

@@ -1,5 +1,6 @@
 // What the grouped-aggregate kernels share (group_agg.hip tt_scan_group, group_extrema.hip
-// tt_scan_extrema, group_sums.hip tt_scan_sums; gfx950 / CDNA4, wave64): the scan front end, the
+// tt_scan_extrema, group_sums.hip tt_scan_sums, and through sparse_cells.h their hashed siblings
+// and group_sparse.hip tt_scan_sparse; gfx950 / CDNA4, wave64): the scan front end, the
 // cell of a row and the launchers' key packing and grid sizing.  ops/columnar.py (cells_of) and the
 // stand-in device of the tests compute the same cell on the host.
 //
@@ -40,15 +41,18 @@ __device__ __forceinline__ uint32_t* stage_bitmaps(uint32_t* lds, const uint32_t
 }
 
 // The block's tiles: each(row0, sel) for every 16-row group of this lane with a selected row,
-// bit i of sel = row row0 + i.  `lds`: where stage_bitmaps put the bitmaps.
-template <typename Each>
+// bit i of sel = row row0 + i.  `lds`: where stage_bitmaps put the bitmaps.  STOP (the hashed
+// kernels, sparse_cells.h): `*stop` is read before each tile and the scan ends once it is set.
+template <bool STOP = false, typename Each>
 __device__ __forceinline__ void scan_tiles(const ColumnDesc* __restrict__ cols, int64_t nrows, int64_t tiles,
                                            const uint16_t* __restrict__ live,  // 1 bit per row, row order
                                            const int32_t* __restrict__ prog, int32_t prog_len,
                                            const uint32_t* __restrict__ bitmaps, int32_t bitmap_words,
-                                           const uint32_t* lds, Each each) {
+                                           const uint32_t* lds, Each each, const uint32_t* stop = nullptr) {
   const bool in_lds = bitmap_words <= kMaxLdsBitmapWords;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if constexpr (STOP)
+      if (__hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
     int64_t row0[kScanU];
     uint16_t lv[kScanU];
 #pragma unroll

@@ -4,7 +4,8 @@
 // non-dropped row whose value the policy `Op` loads:
 //   cnt[cell] += 1;  a[cell] = Op::join_a(a[cell], Op::word_a(v, row));  b[cell] likewise
 // The caller initialises cnt = 0, a = Op::kIdA, b = Op::kIdB.  Integer atomics only
-// (deterministic).  Three instantiations, chosen by the launcher (plan_reduce):
+// (deterministic).  Three instantiations over dense cells, chosen by the launcher (plan_reduce),
+// and one over hashed cells for the *_sparse entry points (plan_reduce_sparse):
 //   kOneCell   no group column: the lane reduces its rows in registers over all its tiles, the
 //              wave reduces across lanes (shuffles), one lane per wave merges into LDS.
 //   kLdsCells  up to kMaxLdsCells cells privatised in LDS (8 + 8 + 4 bytes per cell), flushed once
@@ -12,6 +13,10 @@
 //              in kCopies interleaved copies, lane l on copy l mod kCopies, as tt_scan_group keeps
 //              its few-cell histograms: 64 lanes do not queue on a handful of LDS words.
 //   kGlobalCells  above that, up to tt_group_max_cells(): the rows update the output directly.
+//   kHashedCells  any cell space below 2^62: the 64-bit cell of a row (group_cells64) finds or
+//              claims a slot of the hash table (sparse_slot, sparse_cells.h) after Op::load cleared
+//              the rows without a value -- no slot exists with count 0 -- and the row updates cnt /
+//              a / b at that slot directly; they hold one element per slot.
 // Dynamic LDS: [bitmaps | a | b | cnt], at most 32 + 80 KiB of the CU's 160.
 //
 // Op, a compile-time policy with only what differs:
@@ -23,7 +28,7 @@
 //   merge<LDS>(cnt, a, b, idx, n, x, y)   n rows with words x, y into slot idx, atomically; LDS:
 //                           workgroup scope, the output: agent scope
 #pragma once
-#include "scan_cells.h"
+#include "sparse_cells.h"
 
 extern "C" int tt_group_max_cells();  // group_agg.hip: the cell cap is the histogram's
 
@@ -33,7 +38,7 @@ constexpr int kMaxLdsCells = 4096;          // 20 B each: 80 KiB
 constexpr int kCellBytes = 20;
 constexpr size_t kMaxReduceLds = sizeof(uint32_t) * kMaxLdsBitmapWords + (size_t)kCellBytes * kMaxLdsCells;
 
-enum CellMode : int { kOneCell = 0, kLdsCells = 1, kGlobalCells = 2 };
+enum CellMode : int { kOneCell = 0, kLdsCells = 1, kGlobalCells = 2, kHashedCells = 3 };
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
   return (uint64_t)__shfl_xor((unsigned long long)v, mask, 64);
@@ -45,10 +50,12 @@ __device__ __forceinline__ void scan_reduce(const ColumnDesc* __restrict__ cols,
                                             int32_t prog_len, const uint32_t* __restrict__ bitmaps,
                                             int32_t bitmap_words, const GroupKeys& gk, int32_t ncells,
                                             const typename Op::Args& args, uint32_t* __restrict__ cnt,
-                                            uint64_t* __restrict__ a, uint64_t* __restrict__ b) {
+                                            uint64_t* __restrict__ a, uint64_t* __restrict__ b,
+                                            uint64_t* __restrict__ table_keys = nullptr, uint32_t mask = 0,
+                                            uint32_t* __restrict__ status = nullptr) {  // kHashedCells
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // [bitmaps | a | b | cnt], sized by the launcher
   const uint32_t copies = (MODE == kLdsCells && ncells <= kSpreadCells) ? kCopies : 1;
-  const int slots = MODE == kGlobalCells ? 0 : ncells * (int)copies;
+  const int slots = MODE == kGlobalCells || MODE == kHashedCells ? 0 : ncells * (int)copies;
   uint64_t* s_a = reinterpret_cast<uint64_t*>(stage_bitmaps(lds, bitmaps, bitmap_words));  // 16-byte aligned
   uint64_t* s_b = s_a + slots;
   uint32_t* s_cnt = reinterpret_cast<uint32_t*>(s_b + slots);
@@ -62,7 +69,7 @@ __device__ __forceinline__ void scan_reduce(const ColumnDesc* __restrict__ cols,
   uint32_t r_cnt = 0;                                // kOneCell: the lane's own reduction
   uint64_t r_a = Op::kIdA, r_b = Op::kIdB;
   const ColumnDesc vcd = cols[gk.vcol];
-  scan_tiles(cols, nrows, tiles, live, prog, prog_len, bitmaps, bitmap_words, lds,
+  scan_tiles<MODE == kHashedCells>(cols, nrows, tiles, live, prog, prog_len, bitmaps, bitmap_words, lds,
              [&](int64_t row0, uint32_t sel) __attribute__((always_inline)) {
                typename Op::Value v[16];
                Op::load(vcd, args, row0, sel, v);
@@ -73,6 +80,18 @@ __device__ __forceinline__ void scan_reduce(const ColumnDesc* __restrict__ cols,
                    r_cnt += 1;
                    r_a = Op::join_a(r_a, Op::word_a(v[i], row0 + i));
                    r_b = Op::join_b(r_b, Op::word_b(v[i], row0 + i));
+                 }
+               } else if constexpr (MODE == kHashedCells) {
+                 if (!sel) return;
+                 uint64_t cell[16];
+                 group_cells64(cols, gk, row0, sel, cell);
+#pragma unroll
+                 for (int i = 0; i < 16; ++i) {
+                   if (!((sel >> i) & 1u)) continue;
+                   const uint32_t slot = sparse_slot(table_keys, mask, cell[i], status);
+                   if (slot != kNoSlot)
+                     Op::template merge<false>(cnt, a, b, slot, 1u, Op::word_a(v[i], row0 + i),
+                                               Op::word_b(v[i], row0 + i));
                  }
                } else {
                  if (!sel) return;
@@ -88,7 +107,8 @@ __device__ __forceinline__ void scan_reduce(const ColumnDesc* __restrict__ cols,
                      Op::template merge<false>(cnt, a, b, cell[i], 1u, x, y);
                  }
                }
-             });
+             },
+             status);
   if constexpr (MODE == kOneCell) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -98,7 +118,7 @@ __device__ __forceinline__ void scan_reduce(const ColumnDesc* __restrict__ cols,
     }
     if ((threadIdx.x & 63) == 0 && r_cnt) Op::template merge<true>(s_cnt, s_a, s_b, 0u, r_cnt, r_a, r_b);
   }
-  if constexpr (MODE != kGlobalCells) {
+  if constexpr (MODE != kGlobalCells && MODE != kHashedCells) {
     __syncthreads();
     for (int i = threadIdx.x; i < ncells; i += kScanBlock) {
       uint32_t n = 0;
@@ -139,6 +159,25 @@ inline int plan_reduce(int64_t nrows, int32_t prog_len, int32_t bitmap_words, co
                        : p.mode == kLdsCells && ncells <= kSpreadCells ? (size_t)ncells * kCopies
                                                                         : (size_t)ncells;
   p.lds = bitmap_lds_bytes(bitmap_words) + kCellBytes * slots;
+  p.blocks = resident_blocks(max_blocks, p.lds, p.tiles);
+  return p.blocks < 0 ? (int)p.blocks : 0;
+}
+
+// plan_reduce for the hashed entry points: `slots` as tt_launch_scan_sparse takes them.
+// -1: a bad argument; -2: prod(dims[i] + 1) >= 2^62; -3: as resident_blocks.
+inline int plan_reduce_sparse(int64_t nrows, int32_t prog_len, int32_t bitmap_words, const int32_t* keys,
+                              const int32_t* dims, int32_t nkeys, int32_t value_col, int64_t slots,
+                              int32_t max_blocks, ReducePlan& p) {
+  if (prog_len <= 0 || nrows < 0 || nrows > (int64_t)1 << 32 || bitmap_words <= 0 || value_col < 0 ||
+      max_blocks < 0 || !sparse_slots_ok(slots))
+    return -1;
+  if (const int rc = pack_keys64(keys, dims, nkeys, kMaxValueKeys, p.gk)) return rc;
+  p.gk.vcol = value_col;
+  p.ncells = 0;
+  p.mode = kHashedCells;
+  p.tiles = (nrows + kTileRows - 1) / kTileRows;
+  if (p.tiles == 0) return 0;
+  p.lds = bitmap_lds_bytes(bitmap_words);
   p.blocks = resident_blocks(max_blocks, p.lds, p.tiles);
   return p.blocks < 0 ? (int)p.blocks : 0;
 }
